@@ -1,10 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- HAKAI explicit time step on MI355X: M element-updates/s (hex8, 8 Gauss points).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W [--strong]
+        --master-port P bench.py --gpus N --steps K --warmup W [--strong] [--full]
     python bench.py --local-ranks R          # rehearsal of the N-rank path on one GPU
+
+A plain run does what the headline figure needs and no more: mesh + upload, preload, warm-up, the K
+timed steps, the outputs if --dump-outputs is given, the JSON line. Everything else the line can
+carry is measured only with --full: the other element mode (`config.other_mode`), the nodal/BC
+kernel pass, the deletion window (`config.deletion_window`), the CPU baseline, and for N > 1
+`config.c5_strong`, its `n1_reference` and `single_gpu_same_slab`. Without --full those fields are
+null or absent and the switches that select among them (--compare-fused, --breakdown,
+--deletion-window, --cpu-baseline, --c5-strong, --c5-n1-ref, --same-slab-ref) have no effect.
+
+--dump-outputs DIR writes the state the timed steps left behind (what Solver.download() returns
+right after the last timed step) as DIR/<name>.npy in float64, see dump_outputs(). The inputs are
+generated from fixed seeds, so two builds run with the same arguments can be compared array by array.
 
 A "step" is one full pass of the reference time-loop body (v2/HAKAI_j.jl:497-764): nodal central
 difference with element-order force assembly, prescribed BCs, hex8 B-bar + J2 return + internal
@@ -16,8 +28,8 @@ the north star's 1e-6 on the bench workload (tests/test_gpu_fullsize.py, C3 wind
 oracle) and drifts on the reference's chaotic contact decks only within those decks' own 1-ulp
 sensitivity (tools/oracle_conditioning.py, profiles/r03_oracle_conditioning.jsonl); "exact" is the
 reference-order kernel, whose trajectories equal the CPU restatement of the reference bit for bit
-(tests/test_gpu_exact.py). The line carries the other mode too (`config.other_mode`), timed on the
-same workload in the same process.
+(tests/test_gpu_exact.py). With --full the line carries the other mode too (`config.other_mode`),
+timed on the same workload in the same process.
 
 Workloads (BASELINE.json):
   N = 1 (default)  C3, the 2 M-hex elastoplastic tensile bar 20x20x5000 (Tensile5e steel_Ductile,
@@ -25,8 +37,8 @@ Workloads (BASELINE.json):
   N > 1 (weak)     each rank owns one C3 bar: the 20x20x(5000N) bar in N z-slabs of 20x20x5000
                    (2 M hex each, the same velocity gradient, preload and plastic share as N = 1),
                    so value_N / (N x value_1) compares the same per-GPU work; N = 8 is 16 M hex.
-                   The line also carries `config.c5_strong`: BASELINE config 5, the C5 bar
-                   100x100x1600 (16 M hex) split over the same N ranks, timed in the same run, and the
+                   With --full the line also carries `config.c5_strong`: BASELINE config 5, the
+                   C5 bar 100x100x1600 (16 M hex) split over the same N ranks, timed in the same run, and the
                    same bar on rank 0's GPU alone right after it (`n1_reference`), so `speedup_vs_n1`
                    is a same-run ratio. Every rank builds only its own slab (hakai.dist.bar_slab);
                    `setup_s_per_rank` reports mesh + upload and the first (planning) step per rank.
@@ -37,8 +49,8 @@ Before warm-up an untimed preload advances the bar into its plastic regime (the 
 Gauss points is reported).
 
 Rank 0 prints ONE JSON line. `roofline` is for the dominant (element) kernel, from HIP events on the
-library's stream; `cpu_baseline` is the oracle (CPU restatement of v0.0.2, OpenMP element loop)
-timed on a bounded sample on this host.
+library's stream; `cpu_baseline` (--full) is the oracle (CPU restatement of v0.0.2, OpenMP element
+loop) timed on a bounded sample on this host.
 """
 from __future__ import annotations
 
@@ -61,6 +73,15 @@ B_E_ELASTIC = 1576
 B_N = 224                      # compulsory bytes per node per step (whole step)
 B_N_ELEMENT_SIDE = 72          # coord, u, u_pre read by the element kernel, once per node
 C5_LAYERS = 1600               # C5: 100x100x1600
+# the measurements beside the headline (their 0/1 switches): run only with --full
+FULL_ONLY = ("compare_fused", "breakdown", "deletion_window", "cpu_baseline", "c5_strong", "c5_n1_ref",
+             "same_slab_ref")
+DUMP_MAX_VALUES = 600_000      # --dump-outputs: values per array (10 arrays x 8 bytes: under 64 MB in all)
+DUMP_SEED = 20240607           # seed of the row sample of the larger arrays
+# State fields written by --dump-outputs. Qe is left out: with owner-computed assembly the element
+# kernel keeps node sums only, so the per-element forces of the last step are not an output.
+DUMP_FIELDS = ("disp", "disp_pre", "velo", "Q", "integ_stress", "integ_strain", "integ_yield_stress",
+               "integ_eq_plastic_strain", "integ_triax_stress", "element_flag")
 
 
 def parse():
@@ -68,6 +89,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other element mode, the nodal/BC "
+                         "kernel pass, the deletion window, the CPU baseline, and for N > 1 c5_strong, its N = 1 "
+                         "reference and the same-slab reference (each still has its own 0/1 switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left as DIR/<name>.npy (float64; arrays "
+                         "above %d values as a fixed seeded sample of rows)" % DUMP_MAX_VALUES)
     ap.add_argument("--preload", type=int, default=-1, help="untimed steps before warm-up (-1: config default)")
     ap.add_argument("--layers", type=int, default=0, help="override z layers (tests / quick runs)")
     ap.add_argument("--element-mode", choices=("exact", "fused"), default="fused",
@@ -100,7 +128,11 @@ def parse():
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="--gpus N > 1 outside torch.distributed.run: print the N rank environments the "
                          "launcher would start (one JSON line each) and exit, touching no GPU")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:
+        for k in FULL_ONLY:
+            setattr(a, k, 0)
+    return a
 
 
 TERM_GRACE_S = 30.0            # launcher: SIGTERM -> SIGKILL grace period for the other ranks
@@ -480,6 +512,27 @@ def active_elements(g):
     return sum(int(sv.download(element_flag=True).element_flag.sum()) for sv in g.svs)
 
 
+def dump_outputs(g, ids, nparts, out_dir):
+    """--dump-outputs: the state right after the last timed step, as Solver.download() hands it to a
+    caller (reference layout, State in hakai/solver.py), one float64 DIR/<field>.npy per field of
+    DUMP_FIELDS (element_flag converted from int64); with more than one subdomain <field>_part<r>.npy.
+    An array above the per-array cap is written as a sample of its rows (nodal dofs, Gauss points or
+    elements): sorted row indices drawn without replacement by default_rng(DUMP_SEED) from the
+    array's row count alone, so two runs with the same arguments keep the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_VALUES // nparts
+    for r, sv in zip(ids, g.svs):
+        st = sv.download(**{k: True for k in DUMP_FIELDS})
+        for k in DUMP_FIELDS:
+            x = np.ascontiguousarray(getattr(st, k), dtype=np.float64)
+            width = x.size // max(x.shape[0], 1)
+            keep = max(cap // max(width, 1), 1)
+            if x.shape[0] > keep:
+                rows = np.sort(np.random.default_rng(DUMP_SEED).choice(x.shape[0], size=keep, replace=False))
+                x = x[rows]
+            np.save(os.path.join(out_dir, k + (f"_part{r}" if nparts > 1 else "") + ".npy"), x)
+
+
 DEL_WINDOW_FIRST = 7941        # C3 (v_end 5e5): first ductile deletion wave at step 7950, second at 7953
 DEL_WINDOW_STEPS = 20          # (tests/test_gpu_fullsize.py, tools/diag_fullsize_deletion.py)
 DEL_WINDOW_WARM = 100          # untimed steps per mode between the hand-off and the timed window
@@ -632,6 +685,8 @@ def main():
     # timed region: HIP events around the element kernel (the roofline figure) and the exchange
     elapsed, el_timed, ex_timed = timed(g, t, a.steps, multi)
     t += a.steps
+    if a.dump_outputs:
+        dump_outputs(g, ids, nparts, a.dump_outputs)
     n_active = active_elements(g)
     own_steps = sum(sv.stat("own_steps") for sv in g.svs)
     own_rows = sum(max(sv.stat("own_rows"), 0) for sv in g.svs)

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "hakai-fem_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-REF_TENSILE = "/root/reference/HAKAI-v0.0.0/input/Tensile5e.inp"
+DECKS_GOLDEN = os.path.join(ROOT, "tests", "golden", "decks")
 
 _FIRST = ("test_gpu_exact.py", "test_gpu_configs.py", "test_gpu_fullsize.py", "test_gpu_decks.py",
           "test_gpu_parity.py")
@@ -35,6 +35,25 @@ def pytest_collection_modifyitems(config, items):
             return 100 + _LAST.index(f)
         return 50
     items.sort(key=rank)  # stable: file order within a rank, test order within a file
+
+
+@pytest.fixture(scope="session")
+def ref_decks(tmp_path_factory):
+    """The reference's input decks (v0.0.0-v0.0.2), stored gzipped under tests/golden/decks in the
+    reference's own layout (HAKAI-v0.0.x/input/<deck>.inp.gz), unpacked once per session. Returns
+    the directory that holds the HAKAI-v0.0.x folders."""
+    import gzip
+    import shutil
+    out = tmp_path_factory.mktemp("reference_decks")
+    for d, _, files in os.walk(DECKS_GOLDEN):
+        for f in sorted(files):
+            if not f.endswith(".inp.gz"):
+                continue
+            dst = out / os.path.relpath(d, DECKS_GOLDEN)
+            dst.mkdir(parents=True, exist_ok=True)
+            with gzip.open(os.path.join(d, f), "rb") as src, open(dst / f[:-3], "wb") as fh:
+                shutil.copyfileobj(src, fh)
+    return str(out)
 
 
 @pytest.fixture(scope="session")

@@ -58,6 +58,67 @@ def test_failing_rank_fails_the_launch():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """Without --full every measurement beside the headline is off, whatever its own switch says;
+    with --full the switches keep their defaults and can still be turned off one by one."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3",
+                                      "--deletion-window", "1"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert all(getattr(a, k) == 0 for k in bench.FULL_ONLY)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--cpu-baseline", "0"])
+    a = bench.parse()
+    assert a.full and a.cpu_baseline == 0
+    assert all(getattr(a, k) == 1 for k in bench.FULL_ONLY if k != "cpu_baseline")
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """--dump-outputs: float64 arrays named after the State fields, 64 MB at most in all, the same
+    rows from run to run, small arrays whole."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "hakai-fem_amd"))
+    import bench
+    from hakai.solver import State
+
+    class FakeSolver:
+        def __init__(self, nN, nE):
+            self.st = State.empty(nN, nE)
+            for k in bench.DUMP_FIELDS:
+                x = getattr(self.st, k)
+                x.reshape(-1)[:] = np.arange(x.size) % 1000003
+
+        def download(self, **only):
+            assert set(only) == set(bench.DUMP_FIELDS)
+            return self.st
+
+    class Group:
+        pass
+
+    g = Group()
+    g.svs = [FakeSolver(250_000, 110_000)]
+    for d in ("a", "b"):
+        bench.dump_outputs(g, [0], 1, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in bench.DUMP_FIELDS)
+    total = 0
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and np.array_equal(x, y)
+        assert x.size <= bench.DUMP_MAX_VALUES
+        total += x.nbytes
+    assert total <= 64e6
+    st = g.svs[0].st
+    assert np.array_equal(np.load(tmp_path / "a" / "element_flag.npy"), st.element_flag.astype(np.float64))
+    s = np.load(tmp_path / "a" / "integ_stress.npy")            # sampled rows are whole rows of the source
+    assert s.shape == (bench.DUMP_MAX_VALUES // 6, 6)
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(st.integ_stress.shape[0], size=s.shape[0],
+                                                                 replace=False))
+    assert np.array_equal(s, st.integ_stress[rows])
+
+
 def _devices_check(idents, shared=None):
     """bench.check_distinct_devices on `len(idents)` ranks (threads) over one in-memory store, each
     rank's GPU identity given; returns the per-rank outcome (None or the SystemExit message)."""

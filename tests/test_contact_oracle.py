@@ -99,15 +99,14 @@ def test_contact_pair_surfaces():
     assert total > 10
 
 
-CHARPY = "/root/reference/HAKAI-v0.0.1/input/Charpy-test-v0.0.1.inp"   # read in place, never copied
+CHARPY = "HAKAI-v0.0.1/input/Charpy-test-v0.0.1.inp"   # below the ref_decks fixture (tests/golden/decks)
 
 
-@pytest.mark.skipif(not __import__("os").path.exists(CHARPY), reason="reference decks not present")
-def test_reference_charpy_contact_pairs():
+def test_reference_charpy_contact_pairs(ref_decks):
     """The reference's *Contact Pair deck: 4 instances, 3 pairs with element surfaces. Oracle pairs,
     surface sizes and forces along the run equal the literal restatement."""
     import hakai
-    m = hakai.read_inp(CHARPY)
+    m = hakai.read_inp(f"{ref_decks}/{CHARPY}")
     assert [(a[0], b[0]) for a, b in m.contact_pairs] == [(2, 1), (2, 3), (2, 4)]
     o = O.Oracle(m)
     ref = ContactRef(m)

@@ -9,13 +9,12 @@ import hakai
 from hakai import mesh
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-TENSILE = "/root/reference/HAKAI-v0.0.0/input/Tensile5e.inp"   # read in place, never copied
-REF_DIR = "/root/reference/HAKAI-v0.0.2/input"
+TENSILE = "HAKAI-v0.0.0/input/Tensile5e.inp"   # below the ref_decks fixture (tests/golden/decks, unpacked)
+REF_DIR = "HAKAI-v0.0.2/input"
 
 
-@pytest.mark.skipif(not os.path.exists(TENSILE), reason="reference decks not present")
-def test_tensile5e_reader_matches_code_model():
-    a = hakai.read_inp(TENSILE)
+def test_tensile5e_reader_matches_code_model(ref_decks):
+    a = hakai.read_inp(os.path.join(ref_decks, TENSILE))
     b = mesh.tensile5e_model()
     assert a.nNode == 24 and a.nElement == 5
     assert np.array_equal(a.coordmat, b.coordmat)
@@ -68,12 +67,11 @@ def _py_nodes_elems(path):
     return parts, insts
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference decks not present")
 @pytest.mark.parametrize("deck", ["car-crash-N2k.inp", "car-wall-N2k.inp", "carx2-crash-N43k.inp",
                                   "../../HAKAI-v0.0.1/input/projectile-impact-d1mm.inp"])
-def test_multi_instance_decks(deck):
+def test_multi_instance_decks(ref_decks, deck):
     """Multi-instance decks: translations and rotations of *Instance (v2/readInpFile_j.jl:566-620)."""
-    path = os.path.join(REF_DIR, deck)
+    path = os.path.join(ref_decks, REF_DIR, deck)
     m = hakai.read_inp(path)
     parts, insts = _py_nodes_elems(path)
     coords, elems, off = [], [], 0
@@ -142,12 +140,10 @@ def test_written_decks_round_trip(tmp_path, which):
             assert ia == ib and np.array_equal(ea, eb)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference decks not present")
-def test_every_reference_deck_parses():
+def test_every_reference_deck_parses(ref_decks):
     """readInpFile on every deck the reference ships (v0.0.0-v0.0.2): sizes, positive lumped mass."""
     import glob
-    decks = sorted(glob.glob(os.path.join(os.path.dirname(os.path.dirname(REF_DIR)), "..", "**", "*.inp"),
-                             recursive=True))
+    decks = sorted(glob.glob(os.path.join(ref_decks, "**", "*.inp"), recursive=True))
     assert len(decks) >= 20
     for d in decks:
         m = hakai.read_inp(d)
@@ -156,18 +152,17 @@ def test_every_reference_deck_parses():
         assert np.all(diag > 0), d
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference decks not present")
-def test_deck_fixtures_round_trip():
+def test_deck_fixtures_round_trip(ref_decks):
     """tests/golden/deck_*.npz hold exactly what readInpFile makes of the shipped decks."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
     from deck_fixtures import model_from_arrays, model_to_arrays
-    from make_deck_golden import DECKS, REF
+    from make_deck_golden import DECKS
     gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     for deck, steps, _ in DECKS:
         name = os.path.splitext(os.path.basename(deck))[0].replace("-", "_")
         z = np.load(os.path.join(gold, f"deck_{name}.npz"))
-        m = hakai.read_inp(os.path.join(REF, deck))
+        m = hakai.read_inp(os.path.join(ref_decks, deck))
         assert int(z["steps"]) == (steps or m.n_steps)
         a = model_to_arrays(m)
         for k, v in a.items():

@@ -14,8 +14,9 @@ if [ -n "$SWEEP" ]; then
 timeout -k 10 600 python tools/sweep.py --variants "$SWEEP" > gpurun_out/sweep.log 2>&1
 rc=$?; echo "sweep rc=$rc"; tail -8 gpurun_out/sweep.log; ok $rc || exit $rc
 fi
-timeout -k 10 600 python bench.py --steps 100 --warmup 10 --cpu-seconds 10 > gpurun_out/bench.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -2 gpurun_out/bench.log; [ $rc -eq 0 ] || exit $rc
+BL=${BENCH_LOG:-results/bench.log}; mkdir -p "$(dirname "$BL")"  # the whole line: other mode, deletion window, CPU baseline
+timeout -k 10 600 python bench.py --full --steps 100 --warmup 10 --cpu-seconds 10 > "$BL" 2>&1
+rc=$?; echo "bench rc=$rc"; tail -2 "$BL"; [ $rc -eq 0 ] || exit $rc
 if [ -n "$PROF" ]; then
 P=gpurun_out/prof
 rm -rf $P; mkdir -p $P

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-trace summary of bench.py's deletion window.
 
-`tools/gpu_r6.sh window` runs `bench.py --deletion-window 1 --compare-fused 0 --breakdown 0
+The trace is of `bench.py --full --deletion-window 1 --compare-fused 0 --breakdown 0
 --cpu-baseline 0` under `rocprofv3 --kernel-trace`. Nothing runs after the window, so the last
 2 x steps + 2 element dispatches (k_element_pipe, any instantiation) are, per mode, one untimed
 planning step and the window (headline mode, then the other; bench.deletion_window), and the `steps`
