@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "hakai_exact_math.hpp"
 #include "hakai_kernels.hpp"
 
 namespace hk {
@@ -209,21 +210,6 @@ __device__ __forceinline__ void elem_writeback(const ElemArgs& a, long long e, i
     }
 }
 
-// Ductile table (:720-733): fracture strain at element triaxiality t_e (t_e >= 0), last row
-// outside the bracketing rows.
-__device__ __forceinline__ double ductile_fr(const DevMat* M, int nd, double t_e) {
-#pragma clang fp contract(off)
-    double fr = M->du_eps[nd - 1];
-    for (int j = 0; j + 1 < nd; ++j) {
-        if (t_e >= M->du_tri[j] && t_e < M->du_tri[j + 1]) {
-            fr = M->du_eps[j] + (M->du_eps[j + 1] - M->du_eps[j]) / (M->du_tri[j + 1] - M->du_tri[j]) *
-                                    (t_e - M->du_tri[j]);
-            break;
-        }
-    }
-    return fr;
-}
-
 // One element step for the 8 lanes of a group (every group runs it; the element flag selects what
 // is stored):  flag 1 -> full update;  flag 2 (deleted in the previous step) -> Qe and triaxiality
 // become 0 and the flag 0 (the reference skips deleted elements, :1116, and their stress is zero);
@@ -359,13 +345,7 @@ __device__ __forceinline__ void elem_step(const ElemArgs& a, const DevMat* __res
         sqrt(1.5 * (dv0 * dv0 + dv1 * dv1 + dv2 * dv2 + 2.0 * (fin[3] * fin[3] + fin[4] * fin[4] + fin[5] * fin[5])));
     double sc = 1.0;
     if (ANY_PLASTIC && npp > 0 && q > ys) {
-        int p = npp - 2;  // segment search (:1255-1264), 0-based p = p_index-1
-        for (int j = 1; j < npp; ++j) {
-            if (eqp <= M->pl_eps[j]) {
-                p = j - 1;
-                break;
-            }
-        }
+        const int p = plastic_segment(M->pl_eps, npp, eqp);  // (:1255-1264), 0-based
         const double H = M->Hd[p];
         const double dep = (q - ys) / (3.0 * M->G + H);
         sc = (ys + H * dep) / q;
@@ -398,7 +378,7 @@ __device__ __forceinline__ void elem_step(const ElemArgs& a, const DevMat* __res
         if (!STORE_TRIAX) tri = (oeq < 1e-10) ? 0.0 : mean / oeq;
         const double t_e = allreduce8(tri) * 0.125;
         if (!(t_e < 0.0) && v_e >= M->du_floor)  // (below du_floor no table value is reached)
-            kill = active && v_e >= ductile_fr(M, nd, t_e);  // ductile table (:720-733)
+            kill = active && v_e >= ductile_fr(M->du_eps, M->du_tri, nd, t_e);  // ductile table (:720-733)
     }
 
     // ---- internal force (Qe[:,e] += detJ * Bfinal' * sigma, :1330-1340), reduce-scattered so
@@ -457,31 +437,9 @@ static_assert(kEPB * kLdsStride * 8 == 12800 && kEPB * kFeStride * 8 == 6400 &&
                   kEPB * kXbStride * 8 + 8 * kPusStride * 8 == 20608,
               "own_slot_cap (hakai_kernels.hpp) assumes these LDS sizes");
 
-// x / 3.0 correctly rounded, in two FP64 operations instead of an IEEE division sequence:
-// RN(x*yh + RN(x*yl)) with yh = RN(1/3) and yl = RN(1/3 - yh) = yh * 2^-54 (1/3 = yh + yl + 2^-108/3).
-// The fma's exact operand differs from x/3 by at most |x| * 2^-106 (the double-double reciprocal's
-// remainder plus the rounding of x*yl), while x/3 (a multiple of 1/3 of the result's last place) is
-// either representable or at least 1/6 ulp from every rounding boundary: both round the same way.
-// (Round 5 used q = x*yh, q + (x - 3q)*yh, three operations, which also turned -0 into +0; this
-// form keeps IEEE's -0/3 = -0.) tests/test_div3.py checks the identity against IEEE division on the
-// CPU, zeros and exact multiples included. Normal-range operands (stresses, shape-function
-// derivatives): x*yl stays normal for |x| > 2^-960.
-__device__ __forceinline__ double div3(double x) {
-    constexpr double yh = 1.0 / 3.0;
-    constexpr double yl = 0x1.5555555555555p-56;  // RN(1/3 - yh)
-    return __builtin_fma(x, yh, x * yl);
-}
-
-// a / b correctly rounded given rb = RN(1/b) (one IEEE division per divisor): two Newton-Markstein
-// corrections of q0 = RN(a*rb). q0 is within 1.5 ulp of a/b, q1 within one ulp, and then
-// RN(q1 + (a - b*q1)*rb) is RN(a/b) (Markstein's theorem: the residual is exact for a faithful
-// q1, rb is the correctly rounded reciprocal). Normal-range operands (the element's stresses,
-// volumes); tests/test_div3.py checks it against IEEE division on the CPU.
-__device__ __forceinline__ double div_cr(double a, double b, double rb) {
-    const double q0 = a * rb;
-    const double q1 = __builtin_fma(__builtin_fma(-q0, b, a), rb, q0);
-    return __builtin_fma(__builtin_fma(-q1, b, a), rb, q1);
-}
+// x/3 and a/b correctly rounded without IEEE division sequences: div3 and div_cr, with the
+// hardening-segment search and the ductile table, live in hakai_exact_math.hpp (host and device;
+// the CPU tests compile that header).
 
 // Ordered sum over the 8 Gauss points (lanes) of an element, for every node at once: lane k
 // contributes v[i] for node i; lane i returns ((v_0[i] + v_1[i]) + ...) + v_7[i] (GP order, from
@@ -744,13 +702,7 @@ __device__ __forceinline__ void elem_step_exact(const ElemArgs& a, const DevMat*
         const double q = sqrt(1.5 * (dev[0] * dev[0] + dev[1] * dev[1] + dev[2] * dev[2] + 2.0 * (dev[3] * dev[3]) +
                                      2.0 * (dev[4] * dev[4]) + 2.0 * (dev[5] * dev[5])));
         if (q > ys) {
-            int p = npp - 2;  // segment search (:1255-1264), 0-based p = p_index-1
-            for (int j = 1; j < npp; ++j) {
-                if (eqp <= M->pl_eps[j]) {
-                    p = j - 1;
-                    break;
-                }
-            }
+            const int p = plastic_segment(M->pl_eps, npp, eqp);  // (:1255-1264), 0-based
             const double H = M->Hd[p];
             const double dep = (q - ys) / (3.0 * M->G + H);
             const double s = ys + H * dep;
@@ -799,7 +751,7 @@ __device__ __forceinline__ void elem_step_exact(const ElemArgs& a, const DevMat*
         if (v_e >= M->du_floor) {
             if (!STORE_TRIAX) tri = triax();
             const double t_e = gp_all8(xb, k, tri) * 0.125;
-            if (!(t_e < 0.0)) kill = active && v_e >= ductile_fr(M, nd, t_e);
+            if (!(t_e < 0.0)) kill = active && v_e >= ductile_fr(M->du_eps, M->du_tri, nd, t_e);
         }
     }
 

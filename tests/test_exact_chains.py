@@ -10,13 +10,16 @@ The kernel computes the reference's expressions with three rewrites that are exa
     cal_Bfinal (1/det): (P2_abs/3)*|det| == (P2/3)*det exactly;
   * x/3 and a/b are correctly rounded without IEEE division sequences (div3, div_cr; their own
     check is tests/test_div3.py).
-A C restatement of the kernel's arithmetic (one Gauss point after the other, the same operations
-in the same order as the device lanes, gcc with fma and no contraction) is compared here with the
+A C++ restatement of the kernel's arithmetic (one Gauss point after the other, the same operations
+in the same order as the device lanes, g++ with fma and no contraction) is compared here with the
 oracle on random elements AND on zero-rich ones (axis-aligned cubes whose Jacobians have exact
 zero entries, zero displacement increments, zero stresses, +0/-0 inputs), where the dropped terms
 meet zero accumulators. Every stored output must be bitwise identical, signed zeros included.
+div3, div_cr and the hardening-segment search are not restated: the harness includes
+hakai-fem_amd/csrc/hakai_exact_math.hpp, the header the kernel itself includes.
 The GPU tests (tests/test_gpu_exact.py) then check the kernel itself against the oracle."""
 import ctypes
+import os
 import subprocess
 
 import numpy as np
@@ -26,18 +29,18 @@ from hakai import mesh
 import oracle as O
 from util import bits, random_state, small_bar
 
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hakai-fem_amd", "csrc")
+
 SRC = r"""
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
-static double div3(double x) { const double y = 1.0 / 3.0; const double q = x * y; return fma(fma(-q, 3.0, x), y, q); }
-static double div_cr(double a, double b, double rb) {
-    const double q0 = a * rb;
-    const double q1 = fma(fma(-q0, b, a), rb, q0);
-    return fma(fma(-q1, b, a), rb, q1);
-}
+#include "hakai_exact_math.hpp" /* the kernel's own div3, div_cr, plastic_segment */
+using hk::div3;
+using hk::div_cr;
 
+extern "C" {
 /* One element, the kernel's arithmetic. pus[k][r][i] (192); X[i][3], du[i][3]; sig/eps [8][6],
    eqp/ys [8] in/out; Qe[24] out; mat: Dn, Do, Ds, G, npp, pl_eps[npp], Hd[npp-1]. */
 void elem_exact(const double* pus, const double* X, const double* du, double* sig, double* eps, double* eqp,
@@ -115,10 +118,7 @@ void elem_exact(const double* pus, const double* X, const double* du, double* si
             const double q = sqrt(1.5 * (dev[0] * dev[0] + dev[1] * dev[1] + dev[2] * dev[2] + 2.0 * (dev[3] * dev[3]) +
                                          2.0 * (dev[4] * dev[4]) + 2.0 * (dev[5] * dev[5])));
             if (q > ys[k]) {
-                int p = npp - 2;
-                for (int j = 1; j < npp; ++j)
-                    if (eqp[k] <= pl_eps[j]) { p = j - 1; break; }
-                const double H = Hd[p];
+                const double H = Hd[hk::plastic_segment(pl_eps, npp, eqp[k])];
                 const double dep = (q - ys[k]) / (3.0 * G + H);
                 const double s = ys[k] + H * dep;
                 const double rq = 1.0 / q;
@@ -152,16 +152,17 @@ void elem_exact(const double* pus, const double* X, const double* du, double* si
     for (int k = 0; k < 8; ++k) memcpy(sig + 6 * k, fin[k], sizeof fin[k]);
     *V_out = V;
 }
+}
 """
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
     d = tmp_path_factory.mktemp("exact")
-    c, so = d / "exact.c", d / "exact.so"
+    c, so = d / "exact.cpp", d / "exact.so"
     c.write_text(SRC)
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-mfma", "-shared", "-fPIC", "-o", str(so), str(c), "-lm"],
-                   check=True)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-mfma", "-shared", "-fPIC", "-I", CSRC,
+                    "-o", str(so), str(c)], check=True)
     L = ctypes.CDLL(str(so))
     P = ctypes.c_void_p
     D = ctypes.c_double
