@@ -18,6 +18,7 @@
 #include "../../include/hakai_hip.h"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
+#include "hakai_own_plan.hpp"
 
 using hk::DevMat;
 
@@ -818,390 +819,10 @@ int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Owner-computed assembly (tuning "own_assembly"). Block lb of the persistent element kernel walks
-// a SCHEDULE: the batches at positions [bstart[lb], bstart[lb+1]) of seq, ascending in batch id.
-// A node's incidences, in ascending element order (the reference's serial sum,
-// v2/HAKAI_j.jl:668-675), start with a run held by one block (the head segment). That block sums
-// the run in an LDS slot, starting from 0.0 exactly like the nodal gather, and stores the result
-// into own_q[n] (the whole Q when the run is all of them). Every later contribution is copied
-// unchanged to its own row, rows of a node consecutive in element order, and the nodal kernel
-// forms ((own_q[n] + row) + row) ... -- the same additions in the same order as the gather of fe,
-// so the result is bit-identical whatever the schedule. Rows are numbered by super-batch (an
-// export entry carries up to 4 contributions of any nodes to consecutive rows); own_ridx lists
-// each node's rows in element order. One 16-B entry per node segment piece (or exported
-// contribution) per super-batch of S = 2 schedule positions (1 when 2 would need more than 512
-// entries), one or two per thread (layout: hakai_kernels.hip own_pass). Slots are allocated per
-// block over the super-batches a sum is open; a schedule needing more than own_slot_cap open sums in
-// one block, or a node with > 8 incidences, does not use the mode.
-//
-// Schedules (own_use picks the cheapest that fits):
-//  * contiguous: block lb holds batches [lb*nb/G, (lb+1)*nb/G) -- a slender section (C3) keeps all
-//    of a node layer's sums open in one block;
-//  * banded: on a structured region (element ids x-fastest: the +y neighbour is id+nx, the +z one
-//    id+L) a wide section (C4's 200x200 plate, C5's 100x100 bar) would keep one whole node layer
-//    open (10-40 k sums > 1024 slots), so most contributions became rows. The banded schedule
-//    splits each layer into bands of R element rows and gives each block one band over a run of
-//    layers: a node's 8 incidences then fall in one block unless it sits on a band or run edge.
+// Owner-computed assembly (tuning "own_assembly"): the planner is hakai_own_plan.cpp, the entry
+// format hakai_own_entry.hpp; here the plan is uploaded and switched on and off.
 // ---------------------------------------------------------------------------------------------
-static constexpr int kOwnExpRowsHost = 4;   // = kOwnExpRows: contributions per exported entry
-enum { kOwnInitH = 1, kOwnFinH = 2, kOwnExpH = 4, kOwnNopH = 8 };
-
-struct OwnSched {
-    int epb = 32;                  // elements per batch: 32 (block units) or 8 (wave units)
-    std::vector<int> seq;          // [nb] batch at each position
-    std::vector<long long> bstart; // [G+1]
-    bool banded = false;
-};
-
-struct OwnPlan {
-    int S = 2;
-    std::vector<int> off, list, rp, ridx;
-    long long rows = 0, ne = 0;
-    int max_slots = 1;
-    long long round2 = 0;  // summing passes with more than one entry per thread
-    // per-step bytes the lists add beyond the element/nodal kernels' own (entries read, rows
-    // written and read back, row indices): what own_use compares between schedules
-    double cost() const { return 16.0 * (double)ne + 52.0 * (double)rows; }
-};
-
-static OwnSched own_contiguous(long long nb, long long G, int epb) {
-    OwnSched sc;
-    sc.epb = epb;
-    sc.seq.resize(nb);
-    for (long long b = 0; b < nb; ++b) sc.seq[b] = (int)b;
-    sc.bstart.resize(G + 1);
-    for (long long lb = 0; lb <= G; ++lb) sc.bstart[lb] = lb * nb / G;
-    return sc;
-}
-
-// Lattice strides of structured regions: element e's (nx, L) from a node whose 8 incidences start
-// with e, {e, e+1, e+nx, e+nx+1, e+L, e+L+1, e+L+nx, e+L+nx+1}; elements without such a node (the
-// last of a row, layer or region) take the previous element's. Regions = runs of equal strides.
-// Returns false when the mesh shows no such lattice.
-static bool lattice_strides(const hakai_ctx* c, std::vector<int>& nx, std::vector<int>& L) {
-    const long long nE = c->nE;
-    nx.assign(nE, -1);
-    L.assign(nE, -1);
-    long long found = 0;
-    for (long long e = 0; e < nE; ++e) {
-        for (int k = 0; k < 8; ++k) {
-            const int n = c->h_conn[8 * e + k];
-            const int j0 = c->h_ptr[n];
-            if (c->h_ptr[n + 1] - j0 != 8 || c->h_inc0[j0] / 8 != e) continue;
-            long long q[8];
-            for (int i = 0; i < 8; ++i) q[i] = c->h_inc0[j0 + i] / 8 - e;
-            const long long a = q[2], l = q[4];
-            if (q[1] == 1 && a > 1 && q[3] == a + 1 && l > a + 1 && q[5] == l + 1 && q[6] == l + a &&
-                q[7] == l + a + 1 && l % a == 0 && l < (1LL << 30)) {
-                nx[e] = (int)a;
-                L[e] = (int)l;
-                ++found;
-                break;
-            }
-        }
-    }
-    if (found * 2 < nE) return false;
-    long long first = -1;
-    for (long long e = 0; e < nE; ++e)
-        if (nx[e] > 0) {
-            first = e;
-            break;
-        }
-    for (long long e = 0; e < nE; ++e) {
-        if (nx[e] > 0) continue;
-        const long long src = e < first ? first : e - 1;
-        nx[e] = nx[src];
-        L[e] = L[src];
-    }
-    return true;
-}
-
-// Banded schedule: each batch goes to the band of its first element, (region, row / R); a band's
-// batches (ascending) are cut into runs, about G * (band batches) / nb of them per band.
-// Band height R per region: a band of R element rows keeps up to about R + 1 node rows of sums
-// open in its block -- the R - 1 interior rows of the node layer below, closing row by row while the
-// layer above opens, plus what a super-batch holds (measured with tools/own_plan_check: 1071 slots
-// at R = 4 on a 200-wide section, 1264 at R = 5) -- so R <= slots * 15/16 / (nx + 1) - 1. Within
-// that, the exported rows per node are about 6/R at band edges plus 4 G R / (layers * rows) at run
-// edges, least at R = sqrt(1.5 layers rows / G_region).
-static bool own_banded(const hakai_ctx* c, long long G, const std::vector<int>& nx, const std::vector<int>& L,
-                       int shrink, int epb, int slot_cap, OwnSched& sc) {
-    const long long nb = c->nEp / epb, nE = c->nE;
-    sc.epb = epb;
-    // regions: contiguous id ranges of equal strides
-    std::vector<long long> rstart{0};
-    for (long long x = 1; x < nE; ++x)
-        if (nx[x] != nx[x - 1] || L[x] != L[x - 1]) rstart.push_back(x);
-    rstart.push_back(nE);
-    std::vector<long long> Rreg(rstart.size() - 1);
-    for (size_t r = 0; r + 1 < rstart.size(); ++r) {
-        const long long e0 = rstart[r], ne = rstart[r + 1] - e0;
-        const long long rows = L[e0] / nx[e0], layers = std::max<long long>(1, ne / L[e0]);
-        const double Gr = std::max(1.0, (double)G * (double)ne / (double)nE);
-        const long long Rcap = (slot_cap - slot_cap / 16) / (nx[e0] + 1) - 1;
-        const long long Ropt = (long long)std::llround(std::sqrt(1.5 * (double)layers * (double)rows / Gr));
-        const long long Rwant = c->own_band_rows > 0 ? (long long)c->own_band_rows : std::max<long long>(Ropt, 1);
-        Rreg[r] = std::max<long long>(1, std::min(Rcap, Rwant) - shrink);
-    }
-    std::vector<long long> key(nb);
-    bool any_split = false;
-    size_t region = 0;
-    for (long long b = 0; b < nb; ++b) {
-        const long long e = std::min(epb * b, nE - 1);
-        while (e >= rstart[region + 1]) ++region;
-        const long long rows = L[e] / nx[e];
-        long long R = Rreg[region];
-        if (R >= rows) R = rows;
-        else any_split = true;
-        const long long row = ((e - rstart[region]) % L[e]) / nx[e];
-        key[b] = ((long long)region << 32) | (row / R);
-    }
-    if (!any_split) return false;  // one band per layer everywhere: the contiguous schedule
-    std::vector<int> order(nb);
-    for (long long b = 0; b < nb; ++b) order[b] = (int)b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return key[x] < key[y]; });
-    // bands: [p, q) ranges of the sorted order; runs per band apportioned to exactly G blocks in
-    // total (largest remainders, at least one per band): more blocks than the persistent grid would
-    // run in a second wave (a whole extra block time)
-    std::vector<std::pair<long long, long long>> bands;
-    for (long long p = 0; p < nb;) {
-        long long q = p;
-        while (q < nb && key[order[q]] == key[order[p]]) ++q;
-        bands.emplace_back(p, q);
-        p = q;
-    }
-    const long long nbands = (long long)bands.size();
-    if (nbands > G) return false;
-    std::vector<long long> runs(nbands);
-    std::vector<std::pair<double, long long>> rem;
-    long long used = 0;
-    for (long long i = 0; i < nbands; ++i) {
-        const long long m = bands[i].second - bands[i].first;
-        const double want = (double)G * (double)m / (double)nb;
-        runs[i] = std::max<long long>(1, std::min<long long>(m, (long long)want));
-        used += runs[i];
-        rem.emplace_back(want - (double)runs[i], i);
-    }
-    std::sort(rem.begin(), rem.end(), [](const std::pair<double, long long>& x, const std::pair<double, long long>& y) {
-        return x.first > y.first || (x.first == y.first && x.second < y.second);
-    });
-    for (size_t r = 0; used < G && r < rem.size(); ++r) {
-        const long long i = rem[r].second;
-        if (runs[i] < bands[i].second - bands[i].first) {
-            ++runs[i];
-            ++used;
-        }
-    }
-    for (long long i = 0; used > G && i < nbands; ++i)  // (the minimum of one run per band overshot)
-        while (runs[i] > 1 && used > G) {
-            --runs[i];
-            --used;
-        }
-    sc.seq = order;
-    sc.bstart.assign(1, 0);
-    for (long long i = 0; i < nbands; ++i) {
-        const long long p = bands[i].first, m = bands[i].second - p;
-        for (long long r = 1; r <= runs[i]; ++r) sc.bstart.push_back(p + r * m / runs[i]);
-    }
-    sc.banded = true;
-    return true;
-}
-
-static bool own_plan(const hakai_ctx* c, const OwnSched& sc, int S, int slot_cap, OwnPlan& pl) {
-    const int epb = sc.epb, bs = 8 * epb;  // elements per batch, threads per block
-    const long long nb = c->nEp / epb, nN = c->nN;
-    const long long G = (long long)sc.bstart.size() - 1;
-    if (G <= 0 || c->max_inc > 8 || c->h_ptr.size() != (size_t)nN + 1) return false;
-    pl.S = S;
-    struct Ent { int target, slot, flags, n; int lanes[8]; int inc[4]; };  // inc: an EXP entry's incidences
-    // pos_of[b]: schedule position of batch b; block_of[b]; sb_pos[b] = position of the first batch
-    // of b's super-batch (runs of S positions from each block's first), which indexes the lists
-    std::vector<int> pos_of(nb), block_of(nb);
-    std::vector<long long> sb_pos(nb);
-    for (long long lb = 0; lb < G; ++lb)
-        for (long long p = sc.bstart[lb]; p < sc.bstart[lb + 1]; ++p) {
-            const int b = sc.seq[p];
-            if (p > sc.bstart[lb] && b <= sc.seq[p - 1]) return false;  // ascending within a block
-            pos_of[b] = (int)p;
-            block_of[b] = (int)lb;
-            sb_pos[b] = sc.bstart[lb] + (p - sc.bstart[lb]) / S * S;
-        }
-    std::vector<std::vector<Ent>> per(nb);
-    std::vector<int> rp(nN + 1, 0);
-    long long rows = 0;
-    // open-sum intervals per block in super-batch units: (first, last, entry refs to patch the slot)
-    struct Seg { long long s0, s1; std::vector<std::pair<long long, int>> refs; };
-    std::vector<std::vector<Seg>> segs(G);
-    auto batch_of = [&](int j) { return (long long)(c->h_inc0[j] / 8) / epb; };
-    // LDS lane of incidence j within its super-batch: (position - super-batch position) * epb +
-    // element within the batch, times 8, + local node
-    auto lane_of = [&](int j) {
-        const long long e = c->h_inc0[j] / 8;
-        const long long b = e / epb;
-        return (int)(((pos_of[b] - sb_pos[b]) * epb + e % epb) * 8 + c->h_inc0[j] % 8);
-    };
-    // contributions of later segments: (super-batch, incidence index j); their rows are numbered
-    // in super-batch order so that one entry exports up to 4 of them (any nodes) to consecutive rows
-    std::vector<std::pair<long long, int>> exports;
-    // multi-GPU: the nodes shared with rank-1 send their contributions one by one (hakai_comm.cpp
-    // k_pack_own), so all of them are rows
-    std::vector<char> all_rows(nN, 0);
-    if (const std::vector<int>* dn = hkc::comm_dn_nodes(c))
-        for (int n : *dn) all_rows[n] = 1;
-    for (long long n = 0; n < nN; ++n) {
-        const int j0 = c->h_ptr[n], j1 = c->h_ptr[n + 1];
-        if (j0 == j1) continue;
-        if (all_rows[n]) {
-            for (int j = j0; j < j1; ++j) exports.emplace_back(sb_pos[batch_of(j)], j);
-            continue;
-        }
-        const int hb = block_of[batch_of(j0)];
-        int j = j0;
-        Seg sg;
-        sg.s0 = -1;
-        while (j < j1 && block_of[batch_of(j)] == hb) {  // the head segment, super-batch by super-batch
-            const long long sb = sb_pos[batch_of(j)];
-            Ent en{(int)n, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
-            while (j < j1 && sb_pos[batch_of(j)] == sb) {
-                if (en.n == 8) return false;
-                en.lanes[en.n++] = lane_of(j);
-                ++j;
-            }
-            if (sg.s0 < 0) {
-                sg.s0 = sb;
-                en.flags |= kOwnInitH;
-            }
-            sg.s1 = sb;
-            per[sb].push_back(en);
-            sg.refs.emplace_back(sb, (int)per[sb].size() - 1);
-        }
-        per[sg.s1][sg.refs.back().second].flags |= kOwnFinH;
-        if (sg.s1 > sg.s0) segs[hb].push_back(std::move(sg));
-        for (; j < j1; ++j) exports.emplace_back(sb_pos[batch_of(j)], j);
-    }
-    // rows: grouped by super-batch (stable: node order, then element order within a node)
-    std::stable_sort(exports.begin(), exports.end(),
-                     [](const std::pair<long long, int>& x, const std::pair<long long, int>& y) { return x.first < y.first; });
-    std::vector<int> row_of_inc(c->h_inc0.size(), -1);
-    for (size_t q = 0; q < exports.size();) {
-        const long long sb = exports[q].first;
-        Ent en{0, 0, kOwnExpH, 0, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
-        while (q < exports.size() && exports[q].first == sb && en.n < kOwnExpRowsHost) {
-            const int j = exports[q].second;
-            en.inc[en.n] = j;
-            en.lanes[en.n++] = lane_of(j);
-            ++q;
-        }
-        per[sb].push_back(en);
-    }
-    // Row numbers, coalesced by wave: the EXP entries of a super-batch that one wave of the pass
-    // takes (list positions in one 64-aligned window, a contiguous run: they follow the node
-    // entries) form a group of g entries with m <= 4 g contributions in export order (node, then
-    // element). Contribution q of the group goes to row base + q, dealt to entry q mod g as its
-    // (q / g)-th: so the wave's k-th stores cover g consecutive rows, and a node's rows stay
-    // consecutive for the nodal kernel. An entry's target is base + i, its stride g rides in the
-    // unused slot field.
-    for (long long b = 0; b < nb; ++b) {
-        std::vector<Ent>& v = per[b];
-        for (size_t p = 0; p < v.size();) {
-            if (!(v[p].flags & kOwnExpH)) {
-                ++p;
-                continue;
-            }
-            size_t p1 = p;
-            while (p1 < v.size() && (v[p1].flags & kOwnExpH) && p1 / 64 == p / 64) ++p1;
-            const int g = (int)(p1 - p);
-            std::vector<std::pair<int, int>> cs;  // (incidence, lane) in export order
-            for (size_t i = p; i < p1; ++i)
-                for (int k = 0; k < v[i].n; ++k) cs.emplace_back(v[i].inc[k], v[i].lanes[k]);
-            const int m = (int)cs.size();
-            for (int i = 0; i < g; ++i) {
-                Ent& en = v[p + (size_t)i];
-                en.target = (int)(rows + i);
-                en.slot = g;
-                en.n = 0;
-                for (int q = i; q < m; q += g) {
-                    en.inc[en.n] = cs[(size_t)q].first;
-                    en.lanes[en.n++] = cs[(size_t)q].second;
-                    row_of_inc[cs[(size_t)q].first] = (int)(rows + q);
-                }
-            }
-            rows += m;
-            p = p1;
-        }
-    }
-    // per node: its rows in element order (CSR rp / ridx)
-    std::vector<int>& ridx = pl.ridx;
-    ridx.clear();
-    ridx.reserve(exports.size());
-    for (long long n = 0; n < nN; ++n) {
-        rp[n] = (int)ridx.size();
-        for (int j = c->h_ptr[n]; j < c->h_ptr[n + 1]; ++j)
-            if (row_of_inc[j] >= 0) ridx.push_back(row_of_inc[j]);
-    }
-    rp[nN] = (int)ridx.size();
-    if (rows > (1LL << 31) - 1) return false;
-    // slots: a sum open over super-batches [s0, s1] holds its slot through s1; reuse strictly after
-    int max_slots = 1;
-    for (long long lb = 0; lb < G; ++lb) {
-        auto& v = segs[lb];
-        std::sort(v.begin(), v.end(), [](const Seg& x, const Seg& y) { return x.s0 < y.s0; });
-        std::vector<std::pair<long long, int>> busy;  // (s1, slot) min-heap
-        std::vector<int> free_slots;
-        int next = 0;
-        auto cmp = [](const std::pair<long long, int>& x, const std::pair<long long, int>& y) { return x.first > y.first; };
-        for (auto& sg : v) {
-            while (!busy.empty() && busy.front().first < sg.s0) {
-                free_slots.push_back(busy.front().second);
-                std::pop_heap(busy.begin(), busy.end(), cmp);
-                busy.pop_back();
-            }
-            int slot;
-            if (!free_slots.empty()) {
-                slot = free_slots.back();
-                free_slots.pop_back();
-            } else {
-                slot = next++;
-            }
-            if (slot >= slot_cap) return false;
-            max_slots = std::max(max_slots, slot + 1);
-            for (auto& r : sg.refs) per[r.first][r.second].slot = slot;
-            busy.emplace_back(sg.s1, slot);
-            std::push_heap(busy.begin(), busy.end(), cmp);
-        }
-    }
-    std::vector<int>& off = pl.off;
-    off.assign(nb + 1, 0);
-    for (long long b = 0; b < nb; ++b) {
-        if (per[b].size() > 2 * (size_t)bs) return false;  // two entries per thread at most (own_pass)
-        pl.round2 += per[b].size() > (size_t)bs ? 1 : 0;
-        off[b + 1] = off[b] + (int)per[b].size();
-    }
-    const long long ne = off[nb];
-    std::vector<int>& list = pl.list;
-    list.assign(4 * (size_t)(ne + 1), 0);
-    for (long long b = 0; b < nb; ++b)
-        for (size_t i = 0; i < per[b].size(); ++i) {
-            const Ent& en = per[b][i];
-            unsigned long long lo = 0;
-            for (int q = 0; q < 7; ++q) lo |= (unsigned long long)en.lanes[q] << (9 * q);
-            int* w = &list[4 * ((size_t)off[b] + i)];
-            w[0] = en.target;
-            w[1] = (int)(((unsigned)en.slot & 1023u) | (unsigned)en.flags << 10 | (unsigned)en.n << 14 |
-                         (unsigned)en.lanes[7] << 18 | ((unsigned)en.slot & 1024u) << 18);
-            w[2] = (int)(unsigned)(lo & 0xffffffffu);
-            w[3] = (int)(unsigned)(lo >> 32);
-        }
-    int* nop = &list[4 * (size_t)ne];  // padding entry: reads lane 0, stores to the dump line
-    nop[1] = kOwnNopH << 10;
-    pl.rp = std::move(rp);
-    pl.rows = rows;
-    pl.ne = ne;
-    pl.max_slots = max_slots;
-    return true;
-}
-
-static bool own_upload(hakai_ctx* c, const OwnSched& sc, const OwnPlan& pl) {
+static bool own_upload(hakai_ctx* c, const hk::OwnSched& sc, const hk::OwnPlan& pl) {
     hkc::own_free(c);
     const long long nN = c->nN, G = (long long)sc.bstart.size() - 1;
     std::vector<int> bst(sc.bstart.begin(), sc.bstart.end());
@@ -1256,46 +877,6 @@ static int own_materialize(hakai_ctx* c) {
     return 0;
 }
 
-// Candidate schedules, cheapest plan wins (OwnPlan::cost): contiguous at the persistent grid G0,
-// banded at about G0 blocks (when the mesh has a structured wide section), and, if neither fits,
-// contiguous at 8 G0 (finer ranges keep fewer sums open; the blocks run in waves). Super-batches
-// of 2 batches where they fit 512 entries, else 1. `only` (the CPU replay harness,
-// tools/own_plan_check.cpp): 0 every schedule, 1 contiguous only, 2 banded only.
-static bool own_choose(hakai_ctx* c, long long G0, OwnSched& best_sc, OwnPlan& best, int only = 0) {
-    const int epb = 32;
-    const long long nb = c->nEp / epb;
-    // slots per block: what two blocks per CU leave next to the kernel's own LDS (the wider
-    // passes of S = 2 leave less); row bands are sized for S = 2
-    auto cap_of = [&](int S) { return hk::own_slot_cap(c->elem_exact != 0, S, c->nmat); };
-    const int cap = cap_of(2);
-    bool have = false;
-    auto consider = [&](const OwnSched& sc) {
-        for (int S : {2, 1}) {
-            if (c->own_pass_batches > 0 && S != c->own_pass_batches) continue;
-            OwnPlan pl;
-            if (!own_plan(c, sc, S, cap_of(S), pl)) continue;
-            if (!have || pl.cost() < best.cost()) {
-                best = std::move(pl);
-                best_sc = sc;
-                have = true;
-            }
-            return true;  // S = 2 fits: S = 1 only adds passes
-        }
-        return false;
-    };
-    if (only != 2) consider(own_contiguous(nb, G0, epb));
-    if (only != 1) {
-        std::vector<int> nx, L;
-        if (lattice_strides(c, nx, L)) {
-            OwnSched sc;
-            for (int shrink : {0, 1, 2, 4})  // the widest bands whose open sums fit a block's slots
-                if (own_banded(c, G0, nx, L, shrink, epb, cap, sc) && consider(sc)) break;
-        }
-    }
-    if (!have && only != 2 && 8 * G0 <= nb) consider(own_contiguous(nb, 8 * G0, epb));
-    return have;
-}
-
 static bool own_use(hakai_ctx* c) {
     if (!c->own_assembly || c->nmat > hk::kMaxLdsMats || c->nE <= 0)
         return false;
@@ -1304,9 +885,15 @@ static bool own_use(hakai_ctx* c) {
     bool ok = c->own_built_g > 0;
     if (c->own_for_g0 != G0) {  // not yet built (or found not to fit) for this grid
         if (c->own_valid && own_materialize(c)) return false;  // (multi-GPU: step_once reports it)
-        OwnSched sc;
-        OwnPlan pl;
-        ok = own_choose(c, G0, sc, pl) && own_upload(c, sc, pl);
+        // slots per block: what two blocks per CU leave next to the kernel's own LDS (the wider
+        // passes of S = 2 leave less)
+        const hk::OwnInput in{c->nE, c->nN, c->nEp, c->h_conn, c->h_ptr, c->h_inc0, c->max_inc,
+                              c->own_band_rows, c->own_pass_batches, hkc::comm_dn_nodes(c),
+                              {hk::own_slot_cap(c->elem_exact != 0, 1, c->nmat),
+                               hk::own_slot_cap(c->elem_exact != 0, 2, c->nmat)}};
+        hk::OwnSched sc;
+        hk::OwnPlan pl;
+        ok = hk::own_choose(in, G0, sc, pl) && own_upload(c, sc, pl);
         if (!ok) {
             hkc::own_free(c);
             c->own_built_g = -2;

@@ -169,7 +169,7 @@ __global__ void k_fix(const int* up, int n_up, const int* dn, int n_dn, const in
     }
 }
 
-// Owner-computed assembly (hakai_capi.cpp own_build): a node's local Q is own_q[n] plus its rows
+// Owner-computed assembly (hakai_own_plan.cpp own_plan): a node's local Q is own_q[n] plus its rows
 // (own_ridx[own_rp[n]..]) in element order, and every local contribution of a dn node is a row of
 // its own -- so the partial sums and single contributions below are those k_pack / k_fix take
 // from fe, in the same order.

@@ -127,7 +127,7 @@ struct hakai_ctx {
     long long tdev_next = -1;          // the step the device counter is valid for (-1: unknown)
     int graph = 16;                    // tuning "graph": steps per graph (even), 0 = no capture
     long long graph_steps = 0;         // steps run from graphs (tests, stats)
-    // Owner-computed assembly (tuning "own_assembly", hakai_capi.cpp own_build): the persistent
+    // Owner-computed assembly (tuning "own_assembly", hakai_own_plan.cpp own_plan): the persistent
     // element kernel sums node forces in LDS in element order and stores Q (or a prefix partial plus
     // the later contributions as rows) instead of the per-element fe array.
     int own_assembly = 1;              // tuning value (1 = use when eligible; env HAKAI_OWN_ASSEMBLY)

@@ -864,12 +864,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_element(ElemArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // Owner-computed assembly (ElemArgs::own). The block sums node forces per SUPER-BATCH of OS
-// consecutive batches of its range (the last one may be shorter), one 16-B entry per thread:
-//   x = target (node for ACC entries, row for EXP), y = slot bits 0-9 | flags << 10 | n << 14 |
-//   lane7 << 18 | kOwnRound2 (bit 27, set in the kernel) | slot bit 10 << 28,
-//   z | w << 32 = lanes 0-6, 9 bits each; a lane is ((schedule position of the element's batch -
-//   the super-batch's first position) * 32 + element % 32) * 8 + local node, in ascending element
-//   order.
+// consecutive batches of its range (the last one may be shorter), one 16-B entry per thread
+// (format: hakai_own_entry.hpp).
 // An ACC entry continues node `target`'s running sum in LDS slot `slot` (INIT: from 0.0, the nodal
 // gather's own start) with the super-batch's contributions in element order; FIN stores the sum to
 // own_q (the node's Q, or its prefix partial when later blocks hold more incidences); EXP copies one
@@ -880,9 +876,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_element(ElemArgs a) {
 // LDS running sums per block: what two blocks per CU leave (own_slot_cap, up to 2048), sized per
 // launch to what the lists use (ElemArgs::own_slots, dynamic LDS next to the staged materials)
 // batches per super-batch: 2, or 1 for meshes whose 64-element super-batches need more than 512
-// entries; the host picks (own_choose), the kernel is instantiated for both
-constexpr int kOwnExpRows = 4;            // contributions of one node per EXP entry
-enum { kOwnInit = 1, kOwnFin = 2, kOwnExp = 4, kOwnNop = 8 };
+// entries; the host picks (hakai_own_plan.cpp own_choose), the kernel is instantiated for both
 
 // LDS-only barrier: the pipeline's global prefetches stay in flight.
 __device__ __forceinline__ void lds_barrier() {
@@ -891,10 +885,9 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// The thread's entry of super-batch b, prefetched a batch ahead; bit 27 of .y (free in the list's
-// encoding) marks a super-batch with a second round of entries, so the pass itself loads nothing
-// unless that round exists (a load inside the pass waits for every prefetch issued before it).
-constexpr int kOwnRound2 = 1 << 27;
+// The thread's entry of super-batch b, prefetched a batch ahead; kOwnRound2 in .y (a bit the list's
+// encoding leaves free) marks a super-batch with a second round of entries, so the pass itself loads
+// nothing unless that round exists (a load inside the pass waits for every prefetch issued before it).
 __device__ __forceinline__ int4 own_load(const ElemArgs& a, long long b) {
     const int o0 = a.own_off[b], o1 = a.own_off[b + 1];
     const int idx = o0 + (int)threadIdx.x;
@@ -903,20 +896,16 @@ __device__ __forceinline__ int4 own_load(const ElemArgs& a, long long b) {
     return en;
 }
 
-__device__ __forceinline__ int own_lane(int4 en, int j) {
-    const unsigned long long lo = (unsigned long long)(unsigned)en.z | ((unsigned long long)(unsigned)en.w << 32);
-    return j < 7 ? (int)((lo >> (9 * j)) & 511) : (int)(((unsigned)en.y >> 18) & 511);  // bits 18-26
-}
+__device__ __forceinline__ int own_lane(int4 en, int j) { return own_lane(en.y, en.z, en.w, j); }
 
 __device__ __forceinline__ void own_entry(const ElemArgs& a, int4 en, const double* s_fe, double* s_part) {
 #pragma clang fp contract(off)
-    // slot: bits 0-9 and bit 28 (11 bits); bit 27: kOwnRound2
-    const int slot = (en.y & 1023) | ((en.y >> 18) & 1024), flags = (en.y >> 10) & 15, n = (en.y >> 14) & 15;
+    const int slot = own_slot(en.y), flags = own_flags(en.y), n = own_n(en.y);
     double* dump = a.own_dump + 8 * (long long)blockIdx.x;
     double v[3];
     if (flags & (kOwnExp | kOwnNop)) {  // EXP: up to kOwnExpRows contributions -> rows target + j * stride
         // (stride: the entry's group of EXP entries in this wave, in the slot field; consecutive
-        // lanes write consecutive rows, own_plan)
+        // lanes write consecutive rows, hakai_own_plan.cpp own_plan)
 #pragma unroll
         for (int j = 0; j < kOwnExpRows; ++j) {
             const int l = own_lane(en, j);
@@ -1021,12 +1010,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
     double* xb = s_xb + (EXACT ? grp * kXbStride : 0);
     const long long nb = a.nEp / kEPB;
     // Batch schedule, as (first, stride, count):
-    //  * owner assembly: each block walks a contiguous run of batches, in order (own_build's partition);
+    //  * owner assembly: each block walks a contiguous run of batches, in order (own_plan's partition);
     //  * otherwise each XCD owns a contiguous run and its blocks stride through it together, so the
     //    batches that share a node layer (one element layer apart) are processed close in time on
     //    the same L2 (blocks are dealt round-robin over the 8 XCDs; C3 element reads 2.39 -> 2.20 GB).
     long long first, stride, count;
-    if (OWN) {  // the block's run of schedule positions (own_build: contiguous batches, or row bands)
+    if (OWN) {  // the block's run of schedule positions (own_choose: contiguous batches, or row bands)
         first = a.own_bstart[blockIdx.x];
         stride = 1;
         count = a.own_bstart[blockIdx.x + 1] - first;
@@ -1205,7 +1194,7 @@ hipError_t launch_element(const ElemArgs& a, bool do_delete, bool store_triax, h
     if (a.exact && !a.pusai) return hipErrorInvalidValue;
     const long long nb = a.nEp / kEPB;
     if (nb <= 0) return hipSuccess;
-    if (a.own) {  // owner-computed assembly: persistent kernel only (own_build sized its lists for it)
+    if (a.own) {  // owner-computed assembly: persistent kernel only (own_plan sized its lists for it)
         if (a.own > 2 || a.vol || a.pipe_blocks <= 0 || a.nmat > kMaxLdsMats || !a.own_off || !a.own_list ||
             !a.own_seq || !a.own_bstart || !a.own_q || !a.own_dump || a.own_slots < 1 ||
             a.own_slots > own_slot_cap(a.exact != 0, a.own, a.nmat))

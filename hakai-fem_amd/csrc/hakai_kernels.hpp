@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "hakai_device.hpp"
+#include "hakai_own_entry.hpp"
 
 namespace hk {
 
@@ -40,10 +41,10 @@ struct ElemArgs {
     const double* pusai;    // [8 GP][3][8 nodes] cal_Pusai_hexa table (exact mode)
     const int* poison;      // [0] != 0: a contact buffer overflowed in this call; every state-writing
                             // kernel is a no-op from then on (the state stays the last good step's)
-    // Owner-computed assembly (tuning "own_assembly", hakai_capi.cpp own_build): block lb of the
+    // Owner-computed assembly (tuning "own_assembly", hakai_own_plan.cpp own_plan): block lb of the
     // persistent kernel walks its schedule positions (own_seq, own_bstart) in order and sums every node force
     // it holds in LDS, in element order, from a per-batch list of 16-B entries
-    // (own_list[own_off[b] .. own_off[b+1]), see OwnEntry in hakai_kernels.hip). It stores each
+    // (own_list[own_off[b] .. own_off[b+1]), format: hakai_own_entry.hpp). It stores each
     // node's complete Q, or the prefix partial P of a node whose later incidences belong to later
     // blocks, into own_q, and those later contributions one by one into own_rows. No fe traffic
     // except on a call's last step (STORE_TRIAX), which also stores fe so Q/Qe downloads stay valid.
@@ -105,8 +106,7 @@ struct NodalArgs {
 // per CU (80 KB each) leave next to the kernel's static arrays (node area 12.8 KB, force staging
 // 12 KB per batch of a pass, double-buffered, and in reference-order mode the exchange area and
 // the Pusai table, 20 KB; hakai_kernels.hip checks these sizes) and the staged materials; at most
-// 2048 (11-bit slot ids in the entry lists).
-constexpr int kOwnSlotsMax = 2048;
+// kOwnSlotsMax (11-bit slot ids in the entry lists).
 inline int own_slot_cap(bool exact, int batches_per_pass, int nmat) {
     // (force staging: 6400 B per batch -- 32 elements x 25 doubles, padded -- two buffers)
     const int stat = 12800 + 6400 * batches_per_pass * 2 + (exact ? 20608 : 0) + 64;

@@ -1,7 +1,7 @@
 """Owner-computed assembly plans, replayed on the CPU (tools/own_plan_check.cpp, no GPU).
 
-The planner (hakai_capi.cpp own_choose / own_plan: block schedules, contiguous batch ranges or row
-bands) decides which element-kernel block sums
+The planner (csrc/hakai_own_plan.cpp own_choose / own_plan: block schedules, contiguous batch ranges
+or row bands) decides which element-kernel block sums
 which node contributions in which order. The replay executes each plan as k_element_pipe and k_nodal
 do and checks that every node's Q equals the reference's serial assembly in ascending element order
 (v2/HAKAI_j.jl:668-675) BIT FOR BIT, for random contributions spanning 60 binades -- for slender and
@@ -61,3 +61,14 @@ def test_owner_plan_wide_sections_export_fewer_rows():
     assert res[2]["planned"] and res[2]["banded"] == 1
     if res[1]["planned"]:
         assert res[2]["rows"] < res[1]["rows"], res
+
+
+def test_owner_entry_format_selftest():
+    """Entries packed at the field extremes read back unchanged (csrc/hakai_own_entry.hpp), with and
+    without the kernel's second-round bit."""
+    if not os.path.exists(EXE):
+        pytest.skip("tools/_build/own_plan_check not built")
+    out = subprocess.run([EXE, "--selftest"], capture_output=True, text=True, timeout=30)
+    assert out.returncode == 0, out.stdout + out.stderr
+    r = json.loads(out.stdout.strip().splitlines()[-1])
+    assert r["ok"] and r["bad"] == 0 and r["selftest"] > 0, r

@@ -1,5 +1,6 @@
 // own_plan_check.cpp -- CPU replay of the owner-computed assembly plans (test infrastructure; the
-// planner is host code, hakai_capi.cpp own_choose / own_plan, so it is checked here without a GPU).
+// planner is host code without HIP, csrc/hakai_own_plan.cpp own_choose / own_plan, and this program
+// is built from it and the entry format csrc/hakai_own_entry.hpp alone: no GPU, no product library).
 //
 // Builds a structured hex mesh (hakai.mesh.hex_bar numbering: element id x-fastest, C3D8 node
 // order), or two of them (plate + impactor, C4's shape), optionally with shuffled element ids, runs
@@ -12,13 +13,64 @@
 //
 //   own_plan_check nx ny nz [--plate px py pz] [--G n] [--exact 0|1] [--schedule 0|1|2]
 //                  [--shuffle seed] [--band-rows R]
+//   own_plan_check --selftest
 // Prints one JSON line: {"ok": ..., "planned": ..., "epb", "grid", "superbatch", "banded", "rows",
-// "entries", "slots", "mismatch"} and exits 0 when the replay matches (or no plan fits: planned false).
-#include "../hakai-fem_amd/csrc/hakai_capi.cpp"
-
+// "entries", "slots", "mismatch", "digest"} and exits 0 when the replay matches (or no plan fits:
+// planned false). digest: 64-bit FNV-1a over the plan (epb, S, seq, bstart, off, list, rp, ridx).
+// --selftest packs entries at the field extremes and reads them back (exit 1 on a mismatch).
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <random>
+#include <string>
+#include <vector>
+
+#include "../hakai-fem_amd/csrc/hakai_kernels.hpp"  // own_slot_cap only (host code, no HIP call)
+#include "../hakai-fem_amd/csrc/hakai_own_entry.hpp"
+#include "../hakai-fem_amd/csrc/hakai_own_plan.hpp"
 
 namespace {
+
+struct Fnv {
+    unsigned long long h = 14695981039346656037ull;
+    template <class T>
+    void add(const T& v) {
+        unsigned char b[sizeof(T)];
+        std::memcpy(b, &v, sizeof(T));
+        for (unsigned char x : b) h = (h ^ x) * 1099511628211ull;
+    }
+    template <class T>
+    void add(const std::vector<T>& v) {
+        for (const T& x : v) add(x);
+    }
+};
+
+// Pack and re-read entries at the extremes of every field, with and without the kernel's kOwnRound2.
+int selftest() {
+    long long bad = 0, n_checked = 0;
+    for (int slot : {0, 1023, 1024, hk::kOwnSlotsMax - 1})
+        for (int n = 0; n <= 8; ++n)
+            for (int flags : {0, (int)hk::kOwnInit, (int)hk::kOwnFin, (int)hk::kOwnExp, (int)hk::kOwnNop})
+                for (int pos = 0; pos <= 8; ++pos)  // 8: every lane at the base value
+                    for (int base : {0, 511}) {
+                        int lanes[8], w[4];
+                        for (int j = 0; j < 8; ++j) lanes[j] = j == pos ? 511 - base : base;
+                        const int target = (n_checked & 1) ? INT_MAX : (int)(n_checked % 1000);
+                        hk::own_pack(target, slot, flags, n, lanes, w);
+                        bool ok = w[0] == target && !(w[1] & hk::kOwnRound2);
+                        for (int y : {w[1], w[1] | hk::kOwnRound2}) {
+                            ok = ok && hk::own_slot(y) == slot && hk::own_flags(y) == flags && hk::own_n(y) == n;
+                            for (int j = 0; j < 8; ++j) ok = ok && hk::own_lane(y, w[2], w[3], j) == lanes[j];
+                        }
+                        bad += ok ? 0 : 1;
+                        ++n_checked;
+                    }
+    std::printf("{\"ok\": %s, \"selftest\": %lld, \"bad\": %lld}\n", bad ? "false" : "true", n_checked, bad);
+    return bad ? 1 : 0;
+}
 
 void hex_bar(int nx, int ny, int nz, int node0, std::vector<int>& conn) {
     auto id = [&](int x, int y, int z) { return node0 + x + (nx + 1) * (y + (ny + 1) * z); };
@@ -35,9 +87,10 @@ void hex_bar(int nx, int ny, int nz, int node0, std::vector<int>& conn) {
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 2 && std::string(argv[1]) == "--selftest") return selftest();
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s nx ny nz [--plate px py pz] [--G n] [--exact e] [--schedule s] "
-                     "[--shuffle seed]\n", argv[0]);
+                     "[--shuffle seed] [--band-rows R]\n       %s --selftest\n", argv[0], argv[0]);
         return 2;
     }
     const int nx = std::atoi(argv[1]), ny = std::atoi(argv[2]), nz = std::atoi(argv[3]);
@@ -80,14 +133,7 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 8; ++k) c2[8 * e + k] = conn[8 * (size_t)perm[e] + k];
         conn.swap(c2);
     }
-    hakai_ctx c;
-    c.nE = nE;
-    c.nN = nN;
-    c.nEp = (nE + 31) / 32 * 32;
-    c.h_conn = conn;
-    c.nmat = 1;
-    c.elem_exact = exact;
-    c.own_band_rows = band_rows;
+    const long long nEp = (nE + 31) / 32 * 32;
     // node -> (8e + k) CSR in ascending element order (hakai_upload_model)
     std::vector<int> cnt(nN + 1, 0);
     for (long long e = 0; e < nE; ++e)
@@ -95,17 +141,18 @@ int main(int argc, char** argv) {
     int maxinc = 0;
     for (int n = 0; n < nN; ++n) maxinc = std::max(maxinc, cnt[n + 1]);
     for (int n = 0; n < nN; ++n) cnt[n + 1] += cnt[n];
-    c.h_ptr = cnt;
-    c.h_inc0.assign(8 * (size_t)nE, 0);
+    const std::vector<int>& ptr = cnt;
+    std::vector<int> inc0(8 * (size_t)nE, 0);
     std::vector<int> fill(cnt.begin(), cnt.end() - 1);
     for (long long e = 0; e < nE; ++e)
-        for (int k = 0; k < 8; ++k) c.h_inc0[fill[conn[8 * e + k]]++] = (int)(8 * e + k);
-    c.max_inc = maxinc;
-    const long long G = std::min<long long>(G0, c.nEp / 32);
+        for (int k = 0; k < 8; ++k) inc0[fill[conn[8 * e + k]]++] = (int)(8 * e + k);
+    const hk::OwnInput in{nE, nN, nEp, conn, ptr, inc0, maxinc, band_rows, /*pass_batches*/ 0, /*all_rows*/ nullptr,
+                          {hk::own_slot_cap(exact != 0, 1, 1), hk::own_slot_cap(exact != 0, 2, 1)}};
+    const long long G = std::min<long long>(G0, nEp / 32);
 
-    OwnSched sc;
-    OwnPlan pl;
-    const bool planned = own_choose(&c, G, sc, pl, schedule);
+    hk::OwnSched sc;
+    hk::OwnPlan pl;
+    const bool planned = hk::own_choose(in, G, sc, pl, schedule);
     if (!planned) {
         std::printf("{\"ok\": true, \"planned\": false, \"elements\": %lld, \"nodes\": %d}\n", nE, nN);
         return 0;
@@ -115,7 +162,7 @@ int main(int argc, char** argv) {
     const long long Gp = (long long)sc.bstart.size() - 1;
     std::mt19937_64 rng(12345);
     std::uniform_real_distribution<double> mag(-30.0, 30.0);
-    std::vector<double> f(8 * (size_t)c.nEp, 0.0);
+    std::vector<double> f(8 * (size_t)nEp, 0.0);
     for (long long e = 0; e < nE; ++e)
         for (int k = 0; k < 8; ++k) {
             const double m = std::ldexp(1.0, (int)mag(rng));
@@ -125,10 +172,7 @@ int main(int argc, char** argv) {
     std::vector<char> q_set(nN, 0);
     std::vector<double> slots(4096, 0.0);
     std::vector<double> stage(8 * (size_t)epb * S);
-    auto lane_of = [](const int* w, int j) {
-        const unsigned long long lo = (unsigned long long)(unsigned)w[2] | ((unsigned long long)(unsigned)w[3] << 32);
-        return j < 7 ? (int)((lo >> (9 * j)) & 511) : (int)(((unsigned)w[1] >> 18) & 511);
-    };
+    auto lane_of = [](const int* w, int j) { return hk::own_lane(w[1], w[2], w[3], j); };
     long long bad = 0;
     for (long long lb = 0; lb < Gp; ++lb) {
         for (long long p0 = sc.bstart[lb]; p0 < sc.bstart[lb + 1]; p0 += S) {
@@ -141,16 +185,15 @@ int main(int argc, char** argv) {
                 }
             for (int q = pl.off[p0]; q < pl.off[p0 + 1]; ++q) {
                 const int* w = &pl.list[4 * (size_t)q];
-                const int slot = (w[1] & 1023) | ((w[1] >> 18) & 1024), flags = (w[1] >> 10) & 15,
-                          n = (w[1] >> 14) & 15;
-                if (flags & kOwnExpH) {
+                const int slot = hk::own_slot(w[1]), flags = hk::own_flags(w[1]), n = hk::own_n(w[1]);
+                if (flags & hk::kOwnExp) {
                     for (int j = 0; j < n; ++j) rows[w[0] + (long long)j * slot] = stage[lane_of(w, j)];
                     continue;
                 }
-                if (flags & kOwnNopH) continue;
-                double v = (flags & kOwnInitH) ? 0.0 : slots[slot];
+                if (flags & hk::kOwnNop) continue;
+                double v = (flags & hk::kOwnInit) ? 0.0 : slots[slot];
                 for (int j = 0; j < n; ++j) v += stage[lane_of(w, j)];
-                if (flags & kOwnFinH) {
+                if (flags & hk::kOwnFin) {
                     if (q_set[w[0]]) ++bad;  // a node's sum is finished once
                     q_set[w[0]] = 1;
                     own_q[w[0]] = v;
@@ -163,16 +206,18 @@ int main(int argc, char** argv) {
     long long mismatch = 0;
     for (int n = 0; n < nN; ++n) {
         double ref = 0.0;
-        for (int j = c.h_ptr[n]; j < c.h_ptr[n + 1]; ++j) ref += f[c.h_inc0[j]];
+        for (int j = ptr[n]; j < ptr[n + 1]; ++j) ref += f[inc0[j]];
         double q = own_q[n];
         for (int r = pl.rp[n]; r < pl.rp[n + 1]; ++r) q += rows[pl.ridx[r]];
         if (std::memcmp(&q, &ref, sizeof q) != 0) ++mismatch;
     }
     const bool ok = mismatch == 0 && bad == 0;
+    Fnv dg;
+    dg.add(epb), dg.add(S), dg.add(sc.seq), dg.add(sc.bstart), dg.add(pl.off), dg.add(pl.list), dg.add(pl.rp), dg.add(pl.ridx);
     std::printf("{\"ok\": %s, \"planned\": true, \"elements\": %lld, \"nodes\": %d, \"epb\": %d, \"grid\": %lld, "
                 "\"superbatch\": %d, \"banded\": %d, \"rows\": %lld, \"entries\": %lld, \"slots\": %d, "
-                "\"slot_cap\": %d, \"round2\": %lld, \"mismatch\": %lld, \"double_fin\": %lld}\n",
+                "\"slot_cap\": %d, \"round2\": %lld, \"mismatch\": %lld, \"double_fin\": %lld, \"digest\": \"%016llx\"}\n",
                 ok ? "true" : "false", nE, nN, epb, Gp, S, sc.banded ? 1 : 0, pl.rows, pl.ne, pl.max_slots,
-                hk::own_slot_cap(exact != 0, S, 1), pl.round2, mismatch, bad);
+                in.slot_cap[S - 1], pl.round2, mismatch, bad, dg.h);
     return ok ? 0 : 1;
 }
