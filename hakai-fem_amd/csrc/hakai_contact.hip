@@ -30,6 +30,7 @@
 #include <cstring>
 #include <vector>
 
+#include "hakai_contact_cells.hpp"
 #include "hakai_internal.hpp"
 
 using hkc::fail;
@@ -694,7 +695,7 @@ __global__ __launch_bounds__(kB) void k_ct_bbox(StepIn s, const Seg* segs, const
 __device__ __forceinline__ void bin_rec(const StepIn& s, const Range& r, const PairParam& pp, int pr, int nd,
                                         const double p[3], BRec& e) {
 #pragma clang fp contract(off)
-    for (int d = 0; d < 3; ++d) e.e.m[d] = (long long)ceil((p[d] - r.amn[d]) / pp.ddiv);
+    for (int d = 0; d < 3; ++d) e.e.m[d] = hk::cell_index(p[d], r.amn[d], pp.ddiv);
     const int g = gid(s, nd);
     e.e.node = g;
     e.e.pad = pr;
@@ -890,7 +891,7 @@ __device__ __forceinline__ void tri_geom(int pr, const Range& r, const PairParam
     T.kk = pp.young * S / Lmax * pp.kc;  // :2575
     for (int d = 0; d < 3; ++d) {
         T.q0[d] = q0[d];
-        T.mj[d] = (long long)ceil((q0[d] - r.amn[d]) / pp.ddiv);
+        T.mj[d] = hk::cell_index(q0[d], r.amn[d], pp.ddiv);
     }
     T.c[0] = cx;
     T.c[1] = cy;
@@ -910,34 +911,6 @@ __device__ __forceinline__ void tri_geom(int pr, const Range& r, const PairParam
     T.hoff = pp.hash_off;
     T.hmask = pp.hash_size - 1;
     T.self = pp.self ? 1 : 0;
-}
-
-// Which cells dc (0..26: dx fastest, the reference's dz, dy, dx loops) of the 27 around the
-// candidate's first-node cell can hold an i-node within the candidate's sphere (|p - c| < Rmax,
-// :2532-2536)? A node lies in cell m when ceil((p - amn) / ddiv) == m (bin_rec), i.e. p in
-// (amn + (m-1) ddiv, amn + m ddiv] up to the rounding of that expression. Each box is widened by far
-// more than that rounding and the radius by a relative 1e-9, so a cell is dropped only if no node
-// in it can pass the sphere test: the search visits fewer cells and finds the same events. The
-// squared distance is separable, 3 per axis; NaN geometry keeps every cell. Returns a 27-bit mask.
-__device__ __forceinline__ unsigned reach_mask(const TriRec& T, const double amn[3], double ddiv) {
-    double t2[3][3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double m = (double)(T.mj[d] + (k - 1));
-            const double eps = 1e-9 * ddiv + 1e-12 * (fabs(amn[d]) + fabs(m) * ddiv);
-            const double lo = amn[d] + (m - 1.0) * ddiv - eps, hi = amn[d] + m * ddiv + eps;
-            const double t = fmax(fmax(lo - T.c[d], T.c[d] - hi), 0.0);
-            t2[d][k] = t * t;
-        }
-    const double r = T.Rmax * (1.0 + 1e-9) + 1e-9 * ddiv;
-    const double r2 = r * r * (1.0 + 1e-9);
-    unsigned mask = 0;
-#pragma unroll
-    for (int dc = 0; dc < 27; ++dc)
-        if (!(t2[0][dc % 3] + t2[1][(dc / 3) % 3] + t2[2][dc / 9] > r2)) mask |= 1u << dc;
-    return mask;
 }
 
 // The full prefilter test (:2374-2411) of live triangle j of pair pr with range box r (act: a real
@@ -971,7 +944,8 @@ __device__ __forceinline__ void tri_test(int bid, const StepIn& s, int j, int pr
         double vj[3];
         velo(s, nd0, vj);
         tri_geom(pr, r, pp, gid(s, nd0), gid(s, nd1), gid(s, nd2), ele, p0, p1, p2, vj, T);
-        if (item) mask = reach_mask(T, r.amn, pp.ddiv);  // (small decks: no items, k_ct_tri32)
+        // (small decks: no items, k_ct_tri32)
+        if (item) mask = hk::reach_mask(T.mj, T.c, T.Rmax, r.amn, pp.ddiv);
     }
     const unsigned ni = (unsigned)__popc(mask);
     // the candidate and its items appended with ONE atomic per block (the shard's two counters are

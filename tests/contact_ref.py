@@ -68,6 +68,14 @@ def surface_triangle(faces, keys, owner, contact=None, e0=0, nE=None):
     return tri, tri_e, nodes
 
 
+def _ieee_div(a, b):
+    """a / b as IEEE 754 gives it for a zero divisor too (a zero-area triangle's normal is 0/0 = NaN,
+    which fails every comparison of the event test; Python's float division would raise)."""
+    if b == 0.0:
+        return math.nan if (a == 0.0 or a != a) else math.copysign(math.inf, a) * math.copysign(1.0, b)
+    return a / b
+
+
 class ContactRef:
     def __init__(self, model):
         coord, elem = model.coordmat, model.elementmat
@@ -135,14 +143,15 @@ class ContactRef:
                 c["tri_e"] += tri_e
                 c["tri"] += tri
 
-    def force(self, position, velo, diag_M, element_flag):
-        """position (nN,3), velo (3nN,) -> contact force (3nN,), number of events."""
+    def force(self, position, velo, diag_M, element_flag, log=None):
+        """position (nN,3), velo (3nN,) -> contact force (3nN,), number of events.
+        log: a list that receives (pair index, triangle index in the pair, i-cell, i-node) per event."""
         nN = position.shape[0]
         acc = [Fraction(0)] * (3 * nN)
         d_lim = self.min_size * 0.3
         n_ev = 0
         norm = lambda a, b, c: math.sqrt(a * a + b * b + c * c)  # noqa: E731
-        for c in self.ct:
+        for ci, c in enumerate(self.ct):
             self_ = c["i"] == c["j"]
             P = position
             pi = np.array([P[n - 1] for n in c["nodes_i"]])
@@ -156,7 +165,7 @@ class ContactRef:
             ddiv = self.max_size * (0.6 if self_ else 1.1)
             mapi = [[math.ceil((P[n - 1][d] - amn[d]) / ddiv) for d in range(3)] for n in c["nodes_i"]]
             kc, Cr = (self.kc_s, self.Cr_s) if self_ else (self.kc_o, self.Cr_o)
-            for t, ele in zip(c["tri"], c["tri_e"]):
+            for ti, (t, ele) in enumerate(zip(c["tri"], c["tri_e"])):
                 if element_flag[ele - 1] == 0:
                     continue
                 j0, j1, j2 = t
@@ -176,7 +185,7 @@ class ContactRef:
                 n2 = v1[2] * v2[0] - v1[0] * v2[2]
                 n3 = v1[0] * v2[1] - v1[1] * v2[0]
                 mg = math.sqrt(n1 * n1 + n2 * n2 + n3 * n3)
-                nx, ny, nz = n1 / mg, n2 / mg, n3 / mg
+                nx, ny, nz = _ieee_div(n1, mg), _ieee_div(n2, mg), _ieee_div(n3, mg)
                 d12 = v1[0] * v2[0] + v1[1] * v2[1] + v1[2] * v2[2]
                 S = 0.5 * math.sqrt(L1 * L1 * L2 * L2 - d12 * d12)
                 A11, A21, A31, A12, A22, A32, A13, A23, A33 = v1[0], v1[1], v1[2], v2[0], v2[1], v2[2], -nx, -ny, -nz
@@ -224,4 +233,6 @@ class ContactRef:
                         for tn in (j0, j1, j2):
                             acc[3 * (tn - 1) + q] += Fraction(-val / 3.0)
                     n_ev += 1
+                    if log is not None:
+                        log.append((ci, ti, tuple(mapi[k]), i))
         return np.array([float(a) for a in acc]), n_ev

@@ -191,6 +191,26 @@ def test_contact_group_bitexact_with_deletion(world):
     assert sum(st["candidate_triangles"] > 0 for st in sts) >= 2
 
 
+def test_contact_group_bitexact_with_damping_and_stiffness_factors():
+    """The same deck with contact constants that make the damping term live (Cr != 0, kc != 1): on
+    the multi-GPU path the mass it reads travels in the binned record from Xrank::g_mass, indexed by
+    the GLOBAL node id. Two ranks equal one context bit for bit, and the constants matter."""
+    from hakai import mesh
+    glob = mesh.two_body_model(plate=(6, 6, 1), impactor=(2, 2, 3), v=-3e5, d_time=2e-8, n_steps=400)
+    with Solver(glob) as sv:
+        sv.step(1, glob.n_steps)
+        plain = sv.download()
+    glob.contact_params = (0.25, 1.5, 0.75, 0.125, 0.25)
+    with Solver(glob) as sv:
+        sv.step(1, glob.n_steps)
+        g = sv.download()
+        gdel = [tuple(x) for x in sv.deleted()]
+        gst = sv.contact_stats()
+    assert gst["max_events"] > 0 and not np.array_equal(g.disp, plain.disp)
+    parts = _run_contact_group(glob, 2, glob.n_steps, key=470)
+    _assert_group_equals_single(glob, parts, g, gdel)
+
+
 def test_contact_group_rank_cannot_step_alone():
     """hakai_step on one contact rank of an in-process group is refused BEFORE any work
     (no tsel flip, no prologue kernels), so a later hakai_step_group still matches one context bit
