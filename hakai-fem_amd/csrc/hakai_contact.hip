@@ -1,9 +1,8 @@
 // hakai_contact.hip -- all-exterior instance-vs-instance contact on gfx950.
 //
 // Reference: v2/HAKAI_j.jl (v2 = HAKAI-v0.0.2/Julia)
-//   setup            :244-421   pairs (instance_pair, cp_index), CT lists, element sizes
-//   get_element_face :1944-1992, get_surface_triangle :1996-2164, add_surface_triangle :2167-2245
-//   surface update   :766-804   (after element deletion)
+//   surface update   :766-804   (after element deletion; setup and the surface functions:
+//                               hakai_contact_plan.hpp, where the contact model is planned)
 //   cal_contact_force:2248-2706 (CPU path; the CUDA.jl path :2899-3157 deliberately differs, §9 Q14)
 //   accumulation     :435, :511-538  (Float128 per thread, rounded once into external_force)
 //
@@ -31,6 +30,7 @@
 #include <vector>
 
 #include "hakai_contact_cells.hpp"
+#include "hakai_contact_plan.hpp"
 #include "hakai_internal.hpp"
 
 using hkc::fail;
@@ -43,13 +43,6 @@ using hkc::hip_fail;
     } while (0)
 
 namespace hkc {
-
-struct PairParam {
-    double young, kc, Cr, ddiv;
-    int self;
-    int hash_off, hash_size;
-    int pad;
-};
 
 // Multi-GPU contact (hakai_set_contact_global, §8f-3): owner-computed search. Every rank sets up
 // the contact model of the GLOBAL mesh (the same host enumeration, so the same entries, pairs and
@@ -168,13 +161,13 @@ struct Contact {
     int *d_ni_pair = nullptr, *d_ni_node = nullptr, *d_ni_orig = nullptr, *d_ni_aptr = nullptr, *d_ni_add = nullptr;
     int *d_nj_pair = nullptr, *d_nj_node = nullptr, *d_nj_orig = nullptr, *d_nj_aptr = nullptr, *d_nj_add = nullptr;
     int nseg = 0;
-    int* d_seg = nullptr;  // [nseg] Seg: node-entry segment (start, end, pair, side, region)
+    Seg* d_seg = nullptr;  // [nseg] node-entry segment (start, end, pair, side, region)
     // triangles
     int n_tri = 0;
     int *d_tri_pair = nullptr, *d_tri_nodes = nullptr, *d_tri_ele = nullptr, *d_tri_adder = nullptr;
     // live lists (rebuilt on steps where the surface may have changed)
     int ntile = 0, nreg = 0;
-    void* d_tiles = nullptr;        // [ntile] Tile
+    Tile* d_tiles = nullptr;        // [ntile]
     int *d_tile_cnt = nullptr, *d_tile_off = nullptr;            // [ntile], [ntile+1]
     int* d_reg_first = nullptr;     // [nreg+1] first tile of each region
     int* d_reg = nullptr;           // [nreg][2] (base, live count)
@@ -243,6 +236,9 @@ namespace {
 
 using hkc::Contact;
 using hkc::PairParam;
+using hkc::Seg;
+using hkc::Tile;
+using hkc::kTile;
 using hkc::BEnt;
 using hkc::BRec;
 using hkc::BVel;
@@ -423,7 +419,7 @@ __device__ __forceinline__ void pos(const StepIn& s, int n, double p[3]) {
 // A full rebuild (setup, state upload/reset, a probe, a non-consecutive step) scans everything
 // in tiles of kTile entries that never straddle a region. Lists: 0 i-nodes, 1 j-nodes, 2 triangles.
 constexpr int kTilePer = 8;
-constexpr int kTile = kB * kTilePer;
+static_assert(kTile == kB * kTilePer, "a tile is one block's pass");
 
 struct LiveIn {
     const int *ni_orig, *ni_aptr, *ni_add, *nj_orig, *nj_aptr, *nj_add, *tri_ele, *tri_adder, *flag, *del_step;
@@ -460,10 +456,6 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_w, int& total) {
     total = tot;
     return base + x - v;
 }
-
-struct Tile {
-    int list, start, end, region;
-};
 
 __global__ __launch_bounds__(kB) void k_ct_live_count(const unsigned int* ctl, LiveIn L, const Tile* tiles,
                                                       int ntile, int* tile_cnt) {
@@ -621,13 +613,6 @@ __global__ void k_ct_append(unsigned int* ctl, const int* dlist, AppendIn A, con
 // one pair side. kSegBlocks blocks per segment reduce in registers, then across the block
 // (shuffles + LDS), then issue ONE atomic per bound.
 constexpr int kSegBlocks = 256;
-
-struct Seg {
-    int start, end, pair, side;  // side 0: i-nodes, 1: j-nodes
-    int region;
-    int dup;       // 1: the same live node set as an earlier segment, whose boxes also fill this one's
-    int alias[2];  // bbox offsets (12 pair + 6 side) of up to two such duplicates, -1 if none
-};
 
 __device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
@@ -1948,122 +1933,6 @@ hipError_t upload(T** p, const std::vector<T>& v, hipStream_t s) {
     return hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
-// ---- host: surface extraction with the reference's semantics ------------------------------
-struct Face {
-    int n[4];    // oriented (global 0-based nodes)
-    int key[4];  // sorted
-    int ele;     // global 0-based element
-};
-
-struct Inst {
-    int e0 = -1, nE = 0;
-    std::vector<Face> faces;       // 6 per element, in the reference's order
-    std::vector<int> order;        // face indices sorted by (key, index)
-    std::vector<int> exterior;     // exterior face indices, ascending
-    std::vector<std::vector<int>> added;  // per local element: faces exposed by its deletion
-    double young = 0;
-};
-
-bool key_less(const Face& a, const Face& b) {
-    for (int q = 0; q < 4; ++q)
-        if (a.key[q] != b.key[q]) return a.key[q] < b.key[q];
-    return false;
-}
-bool key_eq(const Face& a, const Face& b) {
-    return a.key[0] == b.key[0] && a.key[1] == b.key[1] && a.key[2] == b.key[2] && a.key[3] == b.key[3];
-}
-
-void build_instance(Inst& I, const std::vector<double>& X, const std::vector<int>& conn) {
-#pragma clang fp contract(off)
-    static const int fidx[6][4] = {{0, 1, 2, 3}, {4, 5, 6, 7}, {0, 1, 5, 4}, {1, 2, 6, 5}, {2, 3, 7, 6}, {3, 0, 4, 7}};
-    const int F = 6 * I.nE;
-    I.faces.resize(F);
-    for (int j = 0; j < I.nE; ++j) {  // get_element_face, :1944-1992
-        const int e = I.e0 + j;
-        const int* el = &conn[8 * (size_t)e];
-        double ctr[3] = {0, 0, 0};
-        for (int a = 0; a < 8; ++a)
-            for (int c = 0; c < 3; ++c) ctr[c] += X[3 * (size_t)el[a] + c];
-        for (int c = 0; c < 3; ++c) ctr[c] /= 8;
-        for (int k = 0; k < 6; ++k) {
-            Face& f = I.faces[6 * j + k];
-            for (int q = 0; q < 4; ++q) f.n[q] = el[fidx[k][q]];
-            const double* x1 = &X[3 * (size_t)f.n[0]];
-            const double* x2 = &X[3 * (size_t)f.n[1]];
-            const double* x4 = &X[3 * (size_t)f.n[3]];
-            const double v1[3] = {x2[0] - x1[0], x2[1] - x1[1], x2[2] - x1[2]};
-            const double v2[3] = {x4[0] - x1[0], x4[1] - x1[1], x4[2] - x1[2]};
-            const double nv[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2],
-                                  v1[0] * v2[1] - v1[1] * v2[0]};
-            const double vc[3] = {ctr[0] - x1[0], ctr[1] - x1[1], ctr[2] - x1[2]};
-            if (nv[0] * vc[0] + nv[1] * vc[1] + nv[2] * vc[2] > 0.) std::swap(f.n[1], f.n[3]);
-            for (int q = 0; q < 4; ++q) f.key[q] = f.n[q];
-            std::sort(f.key, f.key + 4);
-            f.ele = e;
-        }
-    }
-    // faces ordered by (key, index): counting sort on the smallest node, then a stable insertion
-    // sort inside each (tiny) bucket -- linear time at millions of faces
-    I.order.resize(F);
-    {
-        int kmin = INT32_MAX, kmax = -1;
-        for (const Face& f : I.faces) {
-            kmin = std::min(kmin, f.key[0]);
-            kmax = std::max(kmax, f.key[0]);
-        }
-        const int nb = F ? kmax - kmin + 1 : 0;
-        std::vector<int> start((size_t)nb + 1, 0);
-        for (const Face& f : I.faces) start[f.key[0] - kmin + 1]++;
-        for (int b = 0; b < nb; ++b) start[b + 1] += start[b];
-        std::vector<int> fill(start.begin(), start.end() - 1);
-        for (int i = 0; i < F; ++i) I.order[fill[I.faces[i].key[0] - kmin]++] = i;  // ascending index per bucket
-        for (int b = 0; b < nb; ++b)
-            for (int q = start[b] + 1; q < start[b + 1]; ++q) {
-                const int v = I.order[q];
-                int r = q - 1;
-                while (r >= start[b] && key_less(I.faces[v], I.faces[I.order[r]])) {
-                    I.order[r + 1] = I.order[r];
-                    --r;
-                }
-                I.order[r + 1] = v;
-            }
-    }
-    // get_surface_triangle's scan (:2040-2084): in each run of equal keys o1<o2<..<om the scan
-    // pairs (o1,o2), (o3,o4), ...; an odd run keeps its LAST face, unless that is the very last
-    // face of the instance (the loop stops at nE*6-1) -- SURVEY §9 Q13.
-    I.exterior.clear();
-    for (int a = 0; a < F;) {
-        int b = a;
-        while (b < F && key_eq(I.faces[I.order[a]], I.faces[I.order[b]])) ++b;
-        const int m = b - a;
-        const int last = I.order[b - 1];
-        if ((m & 1) && last != F - 1) I.exterior.push_back(last);
-        a = b;
-    }
-    std::sort(I.exterior.begin(), I.exterior.end());
-    // add_surface_triangle (:2167-2245): for each face of the deleted element, the FIRST face (in
-    // face order) with the same key that belongs to another element
-    I.added.assign(I.nE, {});
-    std::vector<int> run_start(F), pos_in_order(F);
-    for (int i = 0; i < F; ++i) pos_in_order[I.order[i]] = i;
-    for (int a = 0; a < F;) {
-        int b = a;
-        while (b < F && key_eq(I.faces[I.order[a]], I.faces[I.order[b]])) ++b;
-        for (int q = a; q < b; ++q) run_start[I.order[q]] = a;
-        a = b;
-    }
-    for (int j = 0; j < I.nE; ++j)
-        for (int k = 0; k < 6; ++k) {
-            const int fi = 6 * j + k;
-            for (int q = run_start[fi]; q < F && key_eq(I.faces[I.order[q]], I.faces[fi]); ++q) {
-                const int cand = I.order[q];
-                if (I.faces[cand].ele == I.e0 + j) continue;
-                I.added[j].push_back(cand);
-                break;
-            }
-        }
-}
-
 }  // namespace
 
 namespace hkc {
@@ -2077,7 +1946,7 @@ void contact_destroy(hakai_ctx* c) {
     dfree(C->d_ni_pair); dfree(C->d_ni_node); dfree(C->d_ni_orig); dfree(C->d_ni_aptr); dfree(C->d_ni_add);
     dfree(C->d_nj_pair); dfree(C->d_nj_node); dfree(C->d_nj_orig); dfree(C->d_nj_aptr); dfree(C->d_nj_add);
     dfree(C->d_tri_pair); dfree(C->d_tri_nodes); dfree(C->d_tri_ele); dfree(C->d_tri_adder);
-    if (C->d_tiles) (void)hipFree(C->d_tiles);
+    dfree(C->d_tiles);
     dfree(C->d_tile_cnt); dfree(C->d_tile_off); dfree(C->d_reg_first); dfree(C->d_reg); dfree(C->d_pair_reg);
     dfree(C->d_el_tri_ptr); dfree(C->d_el_tri); dfree(C->d_el_ni_ptr); dfree(C->d_el_ni); dfree(C->d_el_nj_ptr);
     dfree(C->d_el_nj); dfree(C->d_dlist);
@@ -2410,7 +2279,7 @@ static int step_start(hakai_ctx* c, double t, double d_time) {
             L.nj_orig = C->d_nj_orig; L.nj_aptr = C->d_nj_aptr; L.nj_add = C->d_nj_add;
             L.tri_ele = C->d_tri_ele; L.tri_adder = C->d_tri_adder;
             L.flag = in.flag; L.del_step = del_step; L.t = in.t;
-            const Tile* tl = (const Tile*)C->d_tiles;
+            const Tile* tl = C->d_tiles;
             const unsigned gt = (unsigned)std::min(C->ntile, 2048);
             // full rebuild (forced steps only: the host knows them, so the kernels are not even launched
             // otherwise)
@@ -2431,7 +2300,7 @@ static int step_start(hakai_ctx* c, double t, double d_time) {
     }
     C->force_rebuild = false;
     C->last_t = in.t;
-    const Seg* sg = (const Seg*)C->d_seg;
+    const Seg* sg = C->d_seg;
     if (C->nseg > 0)
         hipLaunchKernelGGL(k_ct_bbox, dim3(C->nseg * C->g_box), dim3(kB), 0, s, in, sg, C->d_reg, C->d_ni_live,
                            C->d_nj_live, C->d_ni_node, C->d_nj_node, bbox, C->g_box);
@@ -2453,7 +2322,7 @@ static int search(hakai_ctx* c, const StepIn& in, bool fused) {
     // the binning and the triangle prefilter in one launch (both need only the boxes; their
     // workgroups run side by side): small decks, and larger ones unless tuned off
     const bool fused_mid = (fused || C->fuse_binfilter) && C->nseg > 0 && C->n_tri > 0;
-    const Seg* sg = (const Seg*)C->d_seg;
+    const Seg* sg = C->d_seg;
     if (C->nseg > 0) {
         if (fused_mid) {
             const int nbin = C->nseg * C->g_seg;
@@ -2543,7 +2412,7 @@ static int xr_a2(hakai_ctx* c, double d_time) {
     {  // (bin block header zeroed by this step's k_ct_reset)
         StepIn in = step_in(c, X->t_a, d_time);
         hipLaunchKernelGGL(k_xr_bin, dim3((unsigned)std::max(1, C->nseg * C->g_seg)), dim3(kB), 0, s, in,
-                           (const Seg*)C->d_seg, C->nseg, C->d_reg, C->d_ni_live, C->d_ni_pair, C->d_ni_node, C->d_par,
+                           C->d_seg, C->nseg, C->d_reg, C->d_ni_live, C->d_ni_pair, C->d_ni_node, C->d_par,
                            xb, nxb, flip, C->npairs, X->d_boxg, X->d_send[1][par], X->capq[1][X->rank], C->g_seg);
     }
     HIPCHK(hipGetLastError());
@@ -2836,365 +2705,66 @@ int contact_check(hakai_ctx* c) {
 
 namespace {
 
-// the mesh contact is set up on: the context's own, or the global one (multi-GPU)
-struct HostMesh {
-    long long nN, nE;
-    const std::vector<double>* coord;  // 3nN
-    const std::vector<int>* conn;      // 8nE, 0-based
-    const std::vector<int>* mat;       // nE, 0-based
-};
-// multi-GPU: the entries this rank keeps (owner-computed search, hkc::Xrank) -- the node entries of
-// the nodes it owns (node_owner = rank of the node's lowest incident element) with local node ids,
-// and the triangles of its elements [E0, E1) with local node and element ids; adders stay global.
-struct OwnFilter {
-    int rank = 0, nranks = 1;
-    const std::vector<int>* node_owner = nullptr;  // [nN global]
-    const std::vector<int>* g2l = nullptr;         // [nN global] local node or -1
-    long long E0 = 0, E1 = 0;
-    std::vector<long long> ni_per_rank;            // out: i-node entries each rank owns
-};
-
-// builds c->contact on mesh H (the surfaces, pairs and entry lists of hakai_set_contact_cp);
-// contact_flag is 1 or 2, c->contact was destroyed by the caller
-int contact_setup(hakai_ctx* c, const HostMesh& H, int32_t contact_flag, const int64_t* element_instance, int32_t n_cp,
-                  const int32_t* cp_instance, const int64_t* cp_elem_off, const int64_t* cp_elems, OwnFilter* own) {
-    const int nE = (int)H.nE;
-    // instances: contiguous element blocks 1, 2, ... (readInpFile numbers them this way)
-    std::vector<Inst> inst;
-    for (int e = 0; e < nE; ++e) {
-        const long long id = element_instance ? element_instance[e] : 1;
-        if (id < 1) return fail(HAKAI_ERR_ARG, "element_instance[%d] = %lld", e + 1, id);
-        if ((size_t)id > inst.size()) {
-            if ((size_t)id != inst.size() + 1)
-                return fail(HAKAI_ERR_ARG, "element_instance must number contiguous element blocks 1, 2, ...");
-            inst.emplace_back();
-            inst.back().e0 = e;
-            inst.back().young = c->h_young[(*H.mat)[e]];
-        } else if ((size_t)id != inst.size()) {
-            return fail(HAKAI_ERR_ARG, "element_instance must number contiguous element blocks 1, 2, ...");
-        }
-        inst.back().nE++;
+// what depends on the kernels' constants: buffer capacities and launch grids (see Contact::g_*)
+void size_for_kernels(Contact* C, const hkc::ContactPlan& P) {
+    long long ci0 = 0, ct0 = 0, maxseg = 1;  // initial contact points and live triangles, longest segment
+    for (int p = 0; p < C->npairs; ++p) {
+        ci0 += C->pair_counts[3 * p];
+        ct0 += C->pair_counts[3 * p + 1];
     }
-    const int ni = (int)inst.size();
-    if (ni == 0) return 0;
-    for (auto& I : inst) build_instance(I, *H.coord, *H.conn);
-    // pairs (:273-311) and CT entries (:332-396). With *Contact Pair surfaces the exterior faces of
-    // each side are restricted to the surface's elements (get_surface_triangle's "pick up only
-    // contact element", :2087-2112 -- applied only when the list is not the whole instance).
-    struct CtDef {
-        int a, b;                                  // a: points (i side), b: triangles (j side)
-        const std::vector<char>* fa = nullptr;     // element filters (instance-local), null = all
-        const std::vector<char>* fb = nullptr;
-    };
-    std::vector<std::vector<char>> filters;
-    filters.reserve(2 * (size_t)n_cp);
-    std::vector<std::pair<int, int>> cp;
-    std::vector<std::pair<const std::vector<char>*, const std::vector<char>*>> cpf;
-    if (n_cp > 0) {
-        for (int k = 0; k < n_cp; ++k) {
-            const std::vector<char>* f[2] = {nullptr, nullptr};
-            int id[2];
-            for (int s = 0; s < 2; ++s) {
-                id[s] = cp_instance[2 * k + s] - 1;
-                if (id[s] < 0 || id[s] >= ni) return fail(HAKAI_ERR_ARG, "contact pair %d: instance %d", k + 1, id[s] + 1);
-                const long long b0 = cp_elem_off[2 * k + s], b1 = cp_elem_off[2 * k + s + 1];
-                std::vector<char> bm((size_t)inst[id[s]].nE, 0);
-                for (long long q = b0; q < b1; ++q) {
-                    const long long el = cp_elems[q];
-                    if (el < 1 || el > inst[id[s]].nE)
-                        return fail(HAKAI_ERR_ARG, "contact pair %d: element %lld not in instance %d", k + 1, el, id[s] + 1);
-                    bm[el - 1] = 1;
-                }
-                if (b1 - b0 != inst[id[s]].nE) {  // the reference compares the list length only (:2087)
-                    filters.push_back(std::move(bm));
-                    f[s] = &filters.back();
-                }
-            }
-            cp.push_back({id[0], id[1]});
-            cpf.push_back({f[0], f[1]});
-        }
-    } else if (ni > 1) {
-        for (int i = 0; i < ni; ++i)
-            for (int j = (contact_flag == 2 ? i : i + 1); j < ni; ++j) {
-                cp.push_back({i, j});
-                cpf.push_back({nullptr, nullptr});
-            }
-    } else {
-        cp.push_back({0, 0});
-        cpf.push_back({nullptr, nullptr});
-    }
-    std::vector<CtDef> ct;
-    for (size_t k = 0; k < cp.size(); ++k) {
-        ct.push_back({cp[k].first, cp[k].second, cpf[k].first, cpf[k].second});
-        if (cp[k].first != cp[k].second) ct.push_back({cp[k].second, cp[k].first, cpf[k].second, cpf[k].first});
-    }
-    auto* C = new hkc::Contact();
-    C->nN = H.nN;
-    C->nE = H.nE;
-    C->npairs = (int)ct.size();
-    // element sizes (:404-421)
-    {
-#pragma clang fp contract(off)
-        double mn = INFINITY, mx = -INFINITY;
-        for (int e = 0; e < nE; ++e) {
-            const int* el = &(*H.conn)[8 * (size_t)e];
-            const double* p1 = &(*H.coord)[3 * (size_t)el[0]];
-            const int oth[3] = {1, 3, 4};
-            for (int q = 0; q < 3; ++q) {
-                const double* p = &(*H.coord)[3 * (size_t)el[oth[q]]];
-                const double a = p1[0] - p[0], b = p1[1] - p[1], d = p1[2] - p[2];
-                const double L = std::sqrt(a * a + b * b + d * d);
-                mn = std::min(mn, L);
-                mx = std::max(mx, L);
-            }
-        }
-        C->min_size = mn;
-        C->max_size = mx;
-        C->d_lim = mn * 0.3;  // :2253
-    }
-    std::vector<int> ni_pair, ni_node, ni_orig, ni_aptr{0}, ni_add;
-    std::vector<int> nj_pair, nj_node, nj_orig, nj_aptr{0}, nj_add;
-    std::vector<int> tri_pair, tri_nodes, tri_ele, tri_adder, seg;
-    struct SegKey {
-        int inst;
-        const void* filt;
-        int adds;
-    };
-    std::vector<SegKey> seg_key;
-    // node list of a pair side: initial exterior nodes + nodes exposed by each element's deletion
-    auto keep = [](const Inst& I, const std::vector<char>* filt, int f) {
-        return !filt || (*filt)[I.faces[f].ele - I.e0];
-    };
-    if (own) own->ni_per_rank.assign((size_t)own->nranks, 0);
-    auto node_list = [&](int pr, const Inst& I, const std::vector<char>* filt, bool with_adds, std::vector<int>& vp,
-                         std::vector<int>& vn, std::vector<int>& vo, std::vector<int>& va, std::vector<int>& vadd,
-                         bool side_i) {
-        // per node: initial (exterior) or the ascending list of elements whose deletion exposes it;
-        // bucketed by node id in linear time (adders arrive in ascending element order)
-        const int nN = (int)H.nN;
-        std::vector<char> orig((size_t)nN, 0), seen((size_t)nN, 0);
-        for (int f : I.exterior)
-            if (keep(I, filt, f))
-                for (int q = 0; q < 4; ++q) orig[I.faces[f].n[q]] = seen[I.faces[f].n[q]] = 1;
-        std::vector<int> cnt((size_t)nN + 1, 0), adders;
-        if (with_adds) {
-            for (int j = 0; j < I.nE; ++j)
-                for (int f : I.added[j])
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = I.faces[f].n[q];
-                        seen[n] = 1;
-                        if (!orig[n]) cnt[n + 1]++;
-                    }
-            for (int n = 0; n < nN; ++n) cnt[n + 1] += cnt[n];
-            adders.resize((size_t)cnt[nN]);
-            std::vector<int> fill(cnt.begin(), cnt.end() - 1);
-            for (int j = 0; j < I.nE; ++j)
-                for (int f : I.added[j])
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = I.faces[f].n[q];
-                        if (!orig[n]) adders[fill[n]++] = I.e0 + j;
-                    }
-        }
-        long long count = 0;
-        for (int n = 0; n < nN; ++n) {
-            if (!seen[n]) continue;
-            if (own) {
-                const int q = (*own->node_owner)[n];
-                if (side_i) own->ni_per_rank[q]++;
-                if (q != own->rank) {
-                    count += orig[n];
-                    continue;
-                }
-            }
-            vp.push_back(pr);
-            vn.push_back(own ? (*own->g2l)[n] : n);
-            vo.push_back(orig[n]);
-            if (!orig[n] && with_adds) {
-                int last = -1;
-                for (int a = cnt[n]; a < cnt[n + 1]; ++a)
-                    if (adders[a] != last) vadd.push_back(last = adders[a]);  // duplicates are adjacent
-            }
-            va.push_back((int)vadd.size());
-            count += orig[n];
-        }
-        return count;
-    };
-    int hoff = 0;
-    for (int pr = 0; pr < C->npairs; ++pr) {
-        const int a = ct[pr].a, b = ct[pr].b;  // a: points (i), b: triangles (j)
-        const bool self = a == b;
-        PairParam pp;
-        pp.young = inst[b].young;  // :367
-        pp.self = self;
-        pp.kc = self ? C->kc_s : C->kc_o;
-        pp.Cr = self ? C->Cr_s : C->Cr_o;
-        pp.ddiv = self ? C->max_size * 0.6 : C->max_size * 1.1;  // :2322-2325
-        const size_t ni0 = ni_node.size(), nj0 = nj_node.size();
-        // surface update (:766-804): c_nodes_i grows for every pair whose point instance lost an
-        // element; triangles and c_nodes_j grow only when the triangle instance differs
-        const long long c_i = node_list(pr, inst[a], ct[pr].fa, true, ni_pair, ni_node, ni_orig, ni_aptr, ni_add, true);
-        const long long c_j =
-            node_list(pr, inst[b], ct[pr].fb, !self, nj_pair, nj_node, nj_orig, nj_aptr, nj_add, false);
-        long long c_t = 0;
-        // a triangle (:2140-2145) of element ele, exposed from the start (adder -1) or by the deletion
-        // of adder; multi-GPU: kept by the rank of ele, with local ids
-        auto add_tri = [&](const int* n, int ele, int adder) {
-            const int tv[6] = {n[0], n[1], n[2], n[2], n[3], n[0]};
-            const bool mine = !own || (ele >= own->E0 && ele < own->E1);
-            for (int h = 0; h < 2; ++h) {
-                if (!mine) continue;
-                tri_pair.push_back(pr);
-                for (int q = 0; q < 3; ++q) tri_nodes.push_back(own ? (*own->g2l)[tv[3 * h + q]] : tv[3 * h + q]);
-                tri_ele.push_back(own ? (int)(ele - own->E0) : ele);
-                tri_adder.push_back(adder);
-            }
-        };
-        for (int f : inst[b].exterior) {
-            if (!keep(inst[b], ct[pr].fb, f)) continue;
-            add_tri(inst[b].faces[f].n, inst[b].faces[f].ele, -1);
-            c_t += 2;
-        }
-        if (!self)
-            for (int j = 0; j < inst[b].nE; ++j)
-                for (int f : inst[b].added[j]) add_tri(inst[b].faces[f].n, inst[b].faces[f].ele, inst[b].e0 + j);
-        // a segment's live node set is a function of (instance, face filter, adders or not): equal
-        // keys, equal sets at every step, so one segment's boxes serve both
-        if (ni_node.size() > ni0) {
-            seg.insert(seg.end(), {(int)ni0, (int)ni_node.size(), pr, 0, -1, 0, -1, -1});
-            seg_key.push_back({a, (const void*)ct[pr].fa, 1});
-        }
-        if (nj_node.size() > nj0) {
-            seg.insert(seg.end(), {(int)nj0, (int)nj_node.size(), pr, 1, -1, 0, -1, -1});
-            seg_key.push_back({b, (const void*)ct[pr].fb, self ? 0 : 1});
-        }
-        // sized for the initial surface; nodes exposed later share buckets (slower, same result)
-        int hs = 64;
-        while (hs < 2 * c_i) hs <<= 1;
-        pp.hash_off = hoff;
-        pp.hash_size = hs;
-        hoff += hs;
-        C->h_par.push_back(pp);
-        C->pair_inst.push_back(a + 1);
-        C->pair_inst.push_back(b + 1);
-        C->pair_counts.push_back(c_i);
-        C->pair_counts.push_back(c_t);
-        C->pair_counts.push_back(c_j);
-    }
-    C->htot = hoff;
-    C->n_ni = (int)ni_node.size();
-    C->n_nj = (int)nj_node.size();
-    C->n_tri = (int)tri_ele.size();
-    C->nseg = (int)seg.size() / 8;
-    for (int q = 0; q < C->nseg; ++q)  // bounding-box duplicates (Seg::dup / alias)
-        for (int r = 0; r < q; ++r) {
-            const SegKey &x = seg_key[q], &y = seg_key[r];
-            if (seg[8 * r + 5] || x.inst != y.inst || x.filt != y.filt || x.adds != y.adds) continue;
-            int* al = &seg[8 * r + 6];
-            const int k = al[0] < 0 ? 0 : (al[1] < 0 ? 1 : -1);
-            if (k < 0) break;  // r already serves two: q computes its own
-            al[k] = 12 * seg[8 * q + 2] + 6 * seg[8 * q + 3];
-            seg[8 * q + 5] = 1;
-            break;
-        }
+    for (const Seg& sg : P.seg) maxseg = std::max<long long>(maxseg, sg.end - sg.start);
     // fused small-deck phases: one 1024-thread workgroup scans the deletion steps, the bucket table
     // and the i-node entries a few times at most
     C->small = C->nE <= (1 << 16) && C->n_ni <= (1 << 16) && C->htot <= (1 << 15);
-    {  // event buffer: 8 events per initial contact point (overflow is detected and reported)
-        long long ci0 = 0;
-        for (int p = 0; p < C->npairs; ++p) ci0 += C->pair_counts[3 * p];
-        C->cap = std::max<long long>(1 << 16, 8LL * ci0);
-        C->cap = (C->cap + kEvShards - 1) / kEvShards * kEvShards;
-    }
-    C->tcap = std::min<long long>(H.nN, 4 * C->cap);
-    {  // launch grids (see Contact::g_*): large models keep the full grids
-        auto clampi = [](long long v, long long lo, long long hi) { return (int)std::max(lo, std::min(hi, v)); };
-        long long ci0 = 0, ct0 = 0, maxseg = 1;
-        for (int p = 0; p < C->npairs; ++p) {
-            ci0 += C->pair_counts[3 * p];
-            ct0 += C->pair_counts[3 * p + 1];
-        }
-        for (int q = 0; q < C->nseg; ++q) maxseg = std::max<long long>(maxseg, seg[8 * q + 1] - seg[8 * q]);
-        C->g_seg = clampi((maxseg + kB - 1) / kB, 1, kSegBlocks);
-        C->g_box = clampi((maxseg + 4 * kB - 1) / (4 * kB), 1, 128);  // ~4 entries per thread: one unrolled pass
-        C->g_ev = clampi((4 * ci0 + kB - 1) / kB, 16, 1024);
-        // >= 64 waves (every event shard); one pass over 16 search items (reachable cells) per live
-        // triangle up to the 4096-block cap -- small self-contact decks keep half their triangles
-        C->g_tri = clampi(((C->small ? 32 : 16) * ct0 + 127) / 128, 32, 4096);  // (small: 32 lanes per candidate)
-        C->g_node = clampi((2 * ci0 + kB - 1) / kB, 4, 256);
-        C->g_del = clampi((C->nE / 4 + kB - 1) / kB, 1, 1024);
-        C->g_reset = clampi((std::max<long long>(std::max<long long>(kEvShards, 12LL * C->npairs), 2 * ci0) + kB - 1) / kB,
-                            1, 64);
-    }
-    // live-list regions: i-node segments, j-node segments, then the triangle list; tiles of
-    // kTile entries inside one region each (full rebuild)
-    std::vector<Tile> tiles;
-    std::vector<int> reg_first, reg;  // reg: [nreg][2] (base, count = 0)
-    std::vector<int> pair_reg(2 * (size_t)C->npairs, -1);
-    auto add_region = [&](int list, int a0, int a1) {
-        const int r = (int)reg_first.size();
-        reg_first.push_back((int)tiles.size());
-        C->reg_list_h.push_back(list);
-        reg.push_back(a0);
-        reg.push_back(0);
-        for (int k = a0; k < a1; k += kTile) tiles.push_back({list, k, std::min(a1, k + kTile), r});
-        return r;
-    };
-    for (int list = 0; list < 2; ++list)
-        for (int q = 0; q < C->nseg; ++q)
-            if (seg[8 * q + 3] == list) {
-                const int r = add_region(list, seg[8 * q], seg[8 * q + 1]);
-                seg[8 * q + 4] = r;
-                pair_reg[2 * (size_t)seg[8 * q + 2] + list] = r;
-            }
-    C->tri_reg = add_region(2, 0, C->n_tri);
-    C->nreg = (int)reg_first.size();
-    reg_first.push_back((int)tiles.size());
-    C->ntile = (int)tiles.size();
-    // element -> entries its deletion exposes (CSR over global element ids)
-    auto invert = [&](const std::vector<int>& aptr, const std::vector<int>& add, int n, std::vector<int>& ptr,
-                      std::vector<int>& idx) {
-        ptr.assign((size_t)nE + 1, 0);
-        for (int k = 0; k < n; ++k)
-            for (int a = aptr[k]; a < aptr[k + 1]; ++a) ptr[add[a] + 1]++;
-        for (int e = 0; e < nE; ++e) ptr[e + 1] += ptr[e];
-        idx.resize((size_t)ptr[nE]);
-        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-        for (int k = 0; k < n; ++k)
-            for (int a = aptr[k]; a < aptr[k + 1]; ++a) idx[fill[add[a]]++] = k;
-    };
-    std::vector<int> el_ni_ptr, el_ni, el_nj_ptr, el_nj, el_tri_ptr, el_tri;
-    invert(ni_aptr, ni_add, C->n_ni, el_ni_ptr, el_ni);
-    invert(nj_aptr, nj_add, C->n_nj, el_nj_ptr, el_nj);
-    {
-        std::vector<int> taptr((size_t)C->n_tri + 1, 0), tadd;
-        for (int j = 0; j < C->n_tri; ++j) {
-            if (tri_adder[j] >= 0) tadd.push_back(tri_adder[j]);
-            taptr[j + 1] = (int)tadd.size();
-        }
-        invert(taptr, tadd, C->n_tri, el_tri_ptr, el_tri);
-    }
+    // event buffer: 8 events per initial contact point (overflow is detected and reported)
+    C->cap = std::max<long long>(1 << 16, 8LL * ci0);
+    C->cap = (C->cap + kEvShards - 1) / kEvShards * kEvShards;
+    C->tcap = std::min<long long>(C->nN, 4 * C->cap);
+    size_cand(C, std::min<long long>(std::max<long long>(C->n_tri, 1), std::max<long long>(1 << 16, 4 * ct0)));
+    // launch grids: large models keep the full grids
+    auto clampi = [](long long v, long long lo, long long hi) { return (int)std::max(lo, std::min(hi, v)); };
+    C->g_seg = clampi((maxseg + kB - 1) / kB, 1, kSegBlocks);
+    C->g_box = clampi((maxseg + 4 * kB - 1) / (4 * kB), 1, 128);  // ~4 entries per thread: one unrolled pass
+    C->g_ev = clampi((4 * ci0 + kB - 1) / kB, 16, 1024);
+    // >= 64 waves (every event shard); one pass over 16 search items (reachable cells) per live
+    // triangle up to the 4096-block cap -- small self-contact decks keep half their triangles
+    C->g_tri = clampi(((C->small ? 32 : 16) * ct0 + 127) / 128, 32, 4096);  // (small: 32 lanes per candidate)
+    C->g_node = clampi((2 * ci0 + kB - 1) / kB, 4, 256);
+    C->g_del = clampi((C->nE / 4 + kB - 1) / kB, 1, 1024);
+    C->g_reset =
+        clampi((std::max<long long>(std::max<long long>(kEvShards, 12LL * C->npairs), 2 * ci0) + kB - 1) / kB, 1, 64);
+}
+
+// builds c->contact on the mesh of `in` (the context's own, or the global one with the entries this
+// rank keeps): plan (hakai_contact_plan.hpp), sizes, upload, buffers; c->contact was destroyed by the caller
+int contact_setup(hakai_ctx* c, const hkc::ContactInput& in, hkc::ContactPlan& P) {
+    if (in.nE == 0) return 0;
+    const std::string err = hkc::contact_plan(in, P);
+    if (!err.empty()) return fail(HAKAI_ERR_ARG, "%s", err.c_str());
+    auto* C = new hkc::Contact();
+    C->kc_o = in.kc_o, C->kc_s = in.kc_s, C->Cr_o = in.Cr_o, C->Cr_s = in.Cr_s;  // what the plan's pairs hold
+    C->nN = in.nN, C->nE = in.nE, C->npairs = (int)P.par.size(), C->h_par = P.par, C->htot = P.htot;
+    C->n_ni = (int)P.ni.node.size(), C->n_nj = (int)P.nj.node.size(), C->n_tri = (int)P.tri_ele.size();
+    C->nseg = (int)P.seg.size(), C->ntile = (int)P.tiles.size(), C->nreg = (int)P.reg_list.size();
+    C->tri_reg = P.tri_reg, C->reg_list_h = P.reg_list, C->pair_inst = P.pair_inst, C->pair_counts = P.pair_counts;
+    C->min_size = P.min_size, C->max_size = P.max_size, C->d_lim = P.d_lim;
+    size_for_kernels(C, P);
     hipStream_t s = c->stream;
+    const hipError_t ups[] = {
+        upload(&C->d_par, P.par, s), upload(&C->d_seg, P.seg, s),
+        upload(&C->d_ni_pair, P.ni.pair, s), upload(&C->d_ni_node, P.ni.node, s), upload(&C->d_ni_orig, P.ni.orig, s),
+        upload(&C->d_ni_aptr, P.ni.aptr, s), upload(&C->d_ni_add, P.ni.add, s),
+        upload(&C->d_nj_pair, P.nj.pair, s), upload(&C->d_nj_node, P.nj.node, s), upload(&C->d_nj_orig, P.nj.orig, s),
+        upload(&C->d_nj_aptr, P.nj.aptr, s), upload(&C->d_nj_add, P.nj.add, s),
+        upload(&C->d_tri_pair, P.tri_pair, s), upload(&C->d_tri_nodes, P.tri_nodes, s),
+        upload(&C->d_tri_ele, P.tri_ele, s), upload(&C->d_tri_adder, P.tri_adder, s),
+        upload(&C->d_reg_first, P.reg_first, s), upload(&C->d_reg, P.reg, s), upload(&C->d_pair_reg, P.pair_reg, s),
+        upload(&C->d_el_ni_ptr, P.el_ni_ptr, s), upload(&C->d_el_ni, P.el_ni, s),
+        upload(&C->d_el_nj_ptr, P.el_nj_ptr, s), upload(&C->d_el_nj, P.el_nj, s),
+        upload(&C->d_el_tri_ptr, P.el_tri_ptr, s), upload(&C->d_el_tri, P.el_tri, s), upload(&C->d_tiles, P.tiles, s)};
     int rc = 0;
-#define UP(dst, v)                                          \
-    do {                                                    \
-        hipError_t _e = upload(&C->dst, v, s);              \
-        if (_e != hipSuccess) rc = hip_fail(_e, #dst);      \
-    } while (0)
-    UP(d_par, C->h_par);
-    UP(d_seg, seg);
-    UP(d_ni_pair, ni_pair); UP(d_ni_node, ni_node); UP(d_ni_orig, ni_orig); UP(d_ni_aptr, ni_aptr); UP(d_ni_add, ni_add);
-    UP(d_nj_pair, nj_pair); UP(d_nj_node, nj_node); UP(d_nj_orig, nj_orig); UP(d_nj_aptr, nj_aptr); UP(d_nj_add, nj_add);
-    UP(d_tri_pair, tri_pair); UP(d_tri_nodes, tri_nodes); UP(d_tri_ele, tri_ele); UP(d_tri_adder, tri_adder);
-    UP(d_reg_first, reg_first); UP(d_reg, reg); UP(d_pair_reg, pair_reg);
-    UP(d_el_ni_ptr, el_ni_ptr); UP(d_el_ni, el_ni); UP(d_el_nj_ptr, el_nj_ptr); UP(d_el_nj, el_nj);
-    UP(d_el_tri_ptr, el_tri_ptr); UP(d_el_tri, el_tri);
-    {
-        Tile* dt = nullptr;
-        hipError_t e = upload(&dt, tiles, s);
-        C->d_tiles = dt;
-        if (e != hipSuccess) rc = hip_fail(e, "d_tiles");
-    }
-#undef UP
+    for (hipError_t e : ups)
+        if (e != hipSuccess) rc = hip_fail(e, "contact_setup: upload");
     c->contact = C;
     if (rc) {
         hkc::contact_destroy(c);
@@ -3207,7 +2777,7 @@ int contact_setup(hakai_ctx* c, const HostMesh& H, int32_t contact_flag, const i
     HIPCHK(dalloc(&C->d_bvel, (size_t)C->blist_cap));
     HIPCHK(dalloc(&C->d_tile_cnt, (size_t)C->ntile));
     HIPCHK(dalloc(&C->d_tile_off, (size_t)C->ntile + 1));
-    HIPCHK(dalloc(&C->d_dlist, (size_t)nE));
+    HIPCHK(dalloc(&C->d_dlist, (size_t)C->nE));
     HIPCHK(dalloc(&C->d_ni_live, (size_t)C->n_ni));
     HIPCHK(dalloc(&C->d_nj_live, (size_t)C->n_nj));
     HIPCHK(dalloc(&C->d_tri_live, (size_t)C->n_tri));
@@ -3217,17 +2787,12 @@ int contact_setup(hakai_ctx* c, const HostMesh& H, int32_t contact_flag, const i
     HIPCHK(hipMemsetAsync(C->d_evs, 0, (size_t)kEvShards * kShardStride * sizeof(unsigned int), s));
     HIPCHK(dalloc(&C->d_ev_nodes, 4 * (size_t)C->cap));
     HIPCHK(dalloc(&C->d_ev_f, 3 * (size_t)C->cap));
-    HIPCHK(dalloc(&C->d_cnt, (size_t)H.nN + 1));
-    HIPCHK(dalloc(&C->d_tpos, (size_t)H.nN + 1));
+    HIPCHK(dalloc(&C->d_cnt, (size_t)C->nN + 1));
+    HIPCHK(dalloc(&C->d_tpos, (size_t)C->nN + 1));
     HIPCHK(dalloc(&C->d_touched[0], (size_t)C->tcap));
     HIPCHK(dalloc(&C->d_touched[1], (size_t)C->tcap));
     HIPCHK(dalloc(&C->d_toff, (size_t)C->tcap));
     HIPCHK(dalloc(&C->d_tcnt, (size_t)C->tcap));
-    {
-        long long t0 = 0;  // initial live triangles
-        for (int p = 0; p < C->npairs; ++p) t0 += C->pair_counts[3 * p + 1];
-        size_cand(C, std::min<long long>(std::max<long long>(C->n_tri, 1), std::max<long long>(1 << 16, 4 * t0)));
-    }
     HIPCHK(dalloc(&C->d_ccnt, (size_t)kCandShards * kShardStride));
     HIPCHK(hipMalloc(&C->d_cand, (size_t)C->cand_cap * sizeof(TriRec)));
     HIPCHK(dalloc(&C->d_item, (size_t)kItemsPerCand * C->cand_cap));
@@ -3235,7 +2800,7 @@ int contact_setup(hakai_ctx* c, const HostMesh& H, int32_t contact_flag, const i
     HIPCHK(dalloc(&C->d_terms, 12 * (size_t)C->cap));
     HIPCHK(dalloc(&C->d_velo0, 3 * (size_t)c->nN));
     HIPCHK(dalloc(&c->d_fext, 3 * (size_t)c->nN));
-    HIPCHK(hipMemsetAsync(C->d_cnt, 0, ((size_t)H.nN + 1) * sizeof(int), s));
+    HIPCHK(hipMemsetAsync(C->d_cnt, 0, ((size_t)C->nN + 1) * sizeof(int), s));
     HIPCHK(hipMemsetAsync(C->d_ctl, 0, kCtl * sizeof(unsigned int), s));
     HIPCHK(hipMemsetAsync(c->d_fext, 0, 3 * (size_t)c->nN * sizeof(double), s));
     C->force_rebuild = true;
@@ -3252,16 +2817,17 @@ int contact_setup(hakai_ctx* c, const HostMesh& H, int32_t contact_flag, const i
 // Multi-GPU (hkc::Xrank) for a contact set up on the global mesh with this rank's entries: the
 // node maps, the global mass and deletion arrays, the exchange blocks; packs the first deletion
 // block if a state exists.
-int xr_build(hakai_ctx* c, const OwnFilter& own, long long nNode, long long nElement, const double* diag_M,
-             const std::vector<int>& g2l, const int64_t* local_node_global, const int64_t* rank_elem_off) {
+int xr_build(hakai_ctx* c, const hkc::ContactOwnership& own, const std::vector<long long>& ni_per_rank, long long nNode,
+             long long nElement, const double* diag_M, const int64_t* local_node_global) {
+    const int64_t* rank_elem_off = own.rank_elem_off;
     hkc::Contact* C = c->contact;
     auto* X = new hkc::Xrank();
     C->xr = X;
     const int nr = own.nranks;
     X->rank = own.rank;
     X->nranks = nr;
-    X->E0 = own.E0;
-    X->nEloc = own.E1 - own.E0;
+    X->E0 = rank_elem_off[own.rank];
+    X->nEloc = rank_elem_off[own.rank + 1] - rank_elem_off[own.rank];
     X->nN_g = nNode;
     X->nE_g = nElement;
     std::vector<long long> eoff((size_t)nr + 1);
@@ -3269,7 +2835,7 @@ int xr_build(hakai_ctx* c, const OwnFilter& own, long long nNode, long long nEle
     for (int q = 0; q < nr; ++q) X->maxEloc = std::max<int>(X->maxEloc, (int)(eoff[q + 1] - eoff[q]));
     long long ci0 = 0, nimax = 1;
     for (int p = 0; p < C->npairs; ++p) ci0 += C->pair_counts[3 * p];
-    for (long long v : own.ni_per_rank) nimax = std::max(nimax, v);
+    for (long long v : ni_per_rank) nimax = std::max(nimax, v);
     // capacities (records per rank block): deletions up to a rank's elements, binned i-nodes up to
     // the entries a rank owns, events up to the event buffer; they start small and grow
     X->cap_max[0] = X->maxEloc;
@@ -3289,7 +2855,7 @@ int xr_build(hakai_ctx* c, const OwnFilter& own, long long nNode, long long nEle
     for (long long n = 0; n < nNode; ++n) gmass[n] = diag_M[3 * n];
     hipStream_t s = c->stream;
     HIPCHK(upload(&X->d_l2g, l2g, s));
-    HIPCHK(upload(&X->d_g2l, g2l, s));
+    HIPCHK(upload(&X->d_g2l, *own.g2l, s));
     HIPCHK(upload(&X->g_mass, gmass, s));
     HIPCHK(upload(&X->d_eoff, eoff, s));
     HIPCHK(dalloc(&X->g_del, (size_t)nElement + 2));
@@ -3339,8 +2905,12 @@ int hakai_set_contact_cp(hakai_ctx* c, int32_t contact_flag, const int64_t* elem
     if (contact_flag > 2) return fail(HAKAI_ERR_ARG, "contact_flag %d (0, 1 or 2)", contact_flag);
     if (c->comm)
         return fail(HAKAI_ERR_STATE, "contact on a rank of a multi-GPU group: use hakai_set_contact_global");
-    const HostMesh H{c->nN, c->nE, &c->h_coord, &c->h_conn, &c->h_mat};
-    return contact_setup(c, H, contact_flag, element_instance, n_cp, cp_instance, cp_elem_off, cp_elems, nullptr);
+    hkc::ContactInput in;
+    in.nN = c->nN, in.nE = c->nE, in.coord = &c->h_coord, in.conn = &c->h_conn, in.mat = &c->h_mat;
+    in.young = &c->h_young, in.contact_flag = contact_flag, in.element_instance = element_instance;
+    in.n_cp = n_cp, in.cp_instance = cp_instance, in.cp_elem_off = cp_elem_off, in.cp_elems = cp_elems;
+    hkc::ContactPlan plan;
+    return contact_setup(c, in, plan);
 }
 
 int hakai_set_contact_global(hakai_ctx* c, int32_t contact_flag, int64_t nNode, const double* coordmat,
@@ -3397,31 +2967,18 @@ int hakai_set_contact_global(hakai_ctx* c, int32_t contact_flag, int64_t nNode, 
                 return fail(HAKAI_ERR_ARG, "set_contact_global: local element %lld differs from global element %lld", e + 1,
                             c->elem_offset + e + 1);
     if (nr > hkc::kMaxXRanks) return fail(HAKAI_ERR_ARG, "set_contact_global: more than %d ranks", hkc::kMaxXRanks);
-    // owner of a node: the rank of its lowest incident element (ranks hold ascending element ranges)
-    std::vector<int> minel((size_t)nNode, INT32_MAX), owner((size_t)nNode, -1);
-    for (int64_t e = 0; e < nElement; ++e)
-        for (int i = 0; i < 8; ++i) {
-            int& m = minel[gconn[8 * e + i]];
-            m = std::min(m, (int)e);
-        }
-    for (int64_t n = 0; n < nNode; ++n)
-        if (minel[n] != INT32_MAX) {
-            const int q = (int)(std::upper_bound(rank_elem_off, rank_elem_off + nr + 1, (int64_t)minel[n]) - rank_elem_off) - 1;
-            owner[n] = q;
-            if (q == rank && g2l[n] < 0)
-                return fail(HAKAI_ERR_ARG, "set_contact_global: owned node %lld is not in the local model", (long long)n + 1);
-        }
-    OwnFilter own;
-    own.rank = rank;
-    own.nranks = nr;
-    own.node_owner = &owner;
-    own.g2l = &g2l;
-    own.E0 = rank_elem_off[rank];
-    own.E1 = rank_elem_off[rank + 1];
-    const HostMesh H{nNode, nElement, &gx, &gconn, &gmat};
-    int rc = contact_setup(c, H, contact_flag, element_instance, n_cp, cp_instance, cp_elem_off, cp_elems, &own);
+    // the plan keeps this rank's entries: those of the nodes it owns and of its elements
+    hkc::ContactOwnership own;
+    own.rank = rank, own.nranks = nr, own.rank_elem_off = rank_elem_off, own.g2l = &g2l;
+    hkc::ContactInput in;
+    in.nN = nNode, in.nE = nElement, in.coord = &gx, in.conn = &gconn, in.mat = &gmat;
+    in.young = &c->h_young, in.contact_flag = contact_flag, in.element_instance = element_instance;
+    in.n_cp = n_cp, in.cp_instance = cp_instance, in.cp_elem_off = cp_elem_off, in.cp_elems = cp_elems;
+    in.own = &own;
+    hkc::ContactPlan plan;
+    int rc = contact_setup(c, in, plan);
     if (rc || !c->contact) return rc;
-    rc = xr_build(c, own, nNode, nElement, diag_M, g2l, local_node_global, rank_elem_off);
+    rc = xr_build(c, own, plan.ni_per_rank, nNode, nElement, diag_M, local_node_global);
     if (rc) hkc::contact_destroy(c);
     return rc;
 }

@@ -137,6 +137,11 @@ double hko_contact_max_size(const hko_contact* c);
 int hko_contact_n_pairs(const hko_contact* c);
 /* out4 = (i_instance, j_instance, #nodes_i, #triangles); returns #nodes_j. */
 int64_t hko_contact_pair_info(const hko_contact* c, int pair, int64_t* out4);
+/* Read-only copy of a pair's lists, sized by hko_contact_pair_info: nodes_i, nodes_j (1-based global
+ * nodes, list order), tri (3 nodes per triangle) and tri_ele (1-based global element per triangle).
+ * A NULL pointer skips that list. Returns 0, or -1 for a bad pair. */
+int hko_contact_pair_lists(const hko_contact* c, int pair, int64_t* nodes_i, int64_t* nodes_j, int64_t* tri,
+                           int64_t* tri_ele);
 
 /* hko_run with contact (c may be NULL): contact force at the top of each step (:500-560) and the
  * surface update after deletions (:766-804). element_instance is needed only with contact. */

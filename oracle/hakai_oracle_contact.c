@@ -386,7 +386,7 @@ void hko_contact_element_deleted(hko_contact* C, const int64_t* element_instance
     }
     for (int64_t i = 0; i < add_tri.n; ++i) iv_push(&add_nodes, add_tri.v[i]);
     iv_unique_inplace(&add_nodes);
-    qsort(add_nodes.v, (size_t)add_nodes.n, sizeof(int64_t), cmp_i64);
+    if (add_nodes.n) qsort(add_nodes.v, (size_t)add_nodes.n, sizeof(int64_t), cmp_i64);  /* (no NULL to qsort) */
     for (int c = 0; c < C->n_ct; ++c) {
         ct_t* T = &C->ct[c];
         if (T->i_inst == ii) {
@@ -623,4 +623,15 @@ int64_t hko_contact_pair_info(const hko_contact* C, int c, int64_t* out4) {
     out4[2] = C->ct[c].nodes_i.n;
     out4[3] = C->ct[c].tri_ele.n;
     return C->ct[c].nodes_j.n;
+}
+
+int hko_contact_pair_lists(const hko_contact* C, int c, int64_t* nodes_i, int64_t* nodes_j, int64_t* tri,
+                           int64_t* tri_ele) {
+    if (c < 0 || c >= C->n_ct) return -1;
+    const ct_t* T = &C->ct[c];
+    if (nodes_i && T->nodes_i.n) memcpy(nodes_i, T->nodes_i.v, sizeof(int64_t) * (size_t)T->nodes_i.n);
+    if (nodes_j && T->nodes_j.n) memcpy(nodes_j, T->nodes_j.v, sizeof(int64_t) * (size_t)T->nodes_j.n);
+    if (tri && T->tri.n) memcpy(tri, T->tri.v, sizeof(int64_t) * (size_t)T->tri.n);
+    if (tri_ele && T->tri_ele.n) memcpy(tri_ele, T->tri_ele.v, sizeof(int64_t) * (size_t)T->tri_ele.n);
+    return 0;
 }
