@@ -49,7 +49,7 @@ struct Comm {
     std::vector<int> h_dn;                       // host copy of d_dn (owner-computed assembly)
     bool pending = false;
     int pending_par = 0;
-    // collectives of the multi-GPU contact (hakai_contact.hip) on cs, handed over by events
+    // collectives of the multi-GPU contact (hakai_contact_xr.hip) on cs, handed over by events
     hipEvent_t ev_ag_ready = nullptr, ev_ag_done = nullptr;
 };
 
@@ -344,7 +344,7 @@ int comm_rank(const hakai_ctx* c) { return c->comm ? c->comm->rank : 0; }
 int comm_size(const hakai_ctx* c) { return c->comm ? c->comm->nranks : 1; }
 
 // RCCL only: recv[q*bytes .. (q+1)*bytes) = rank q's `send`, ordered on c->stream (the divided
-// contact search's per-step event exchange, hakai_contact.hip)
+// contact search's per-step event exchange, hakai_contact_xr.hip)
 int comm_allgather_raw(hakai_ctx* c, const void* send, void* recv, size_t bytes) {
     Comm* m = c->comm;
     if (!m || m->mode != 0) return fail(HAKAI_ERR_STATE, "all-gather: not an RCCL communicator");
@@ -379,7 +379,7 @@ int comm_allgatherv_raw(hakai_ctx* c, const void* send, void* recv, const size_t
 }
 
 // RCCL only: recv = elementwise MIN over the ranks of send (uint64 words), ordered on c->stream
-// (the multi-GPU contact's pair boxes, hakai_contact.hip)
+// (the multi-GPU contact's pair boxes, hakai_contact_xr.hip)
 int comm_allreduce_min_u64(hakai_ctx* c, const void* send, void* recv, size_t count) {
     Comm* m = c->comm;
     if (!m || m->mode != 0) return fail(HAKAI_ERR_STATE, "all-reduce: not an RCCL communicator");

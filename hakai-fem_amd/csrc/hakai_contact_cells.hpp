@@ -1,4 +1,4 @@
-// hakai_contact_cells.hpp -- the cell grid of the contact search (hakai_contact.hip): the cell index
+// hakai_contact_cells.hpp -- the cell grid of the contact search (hakai_contact_dev.hpp): the cell index
 // of a point and the cull of the 27 neighbour cells by a candidate triangle's bounding sphere. One
 // source for the device and for the CPU test: tests/test_reach_mask.py compiles THIS file with a
 // host compiler (no contraction) and holds reach_mask against a plain restatement of the

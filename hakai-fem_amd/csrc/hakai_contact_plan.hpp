@@ -34,7 +34,7 @@ namespace hkc {
 // local node and element ids; adders stay global.
 // ---------------------------------------------------------------------------------------------
 
-// Layouts shared with the device (hakai_contact.hip).
+// Layouts shared with the device (hakai_contact.hip, hakai_contact_xr.hip).
 struct PairParam {
     double young, kc, Cr, ddiv;
     int self;

@@ -10,7 +10,7 @@
 
 namespace hkc {
 struct Comm;     // multi-GPU state (hakai_comm.cpp)
-struct Contact;  // contact search state (hakai_contact.hip)
+struct Contact;  // contact search state (hakai_contact_state.hpp)
 int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 }  // namespace hkc
@@ -104,7 +104,7 @@ struct hakai_ctx {
     std::vector<int> h_conn;      // 8nE, 0-based
     std::vector<int> h_mat;       // nE, 0-based
     std::vector<double> h_young;  // per material
-    // external force (contact) -- null until contact is enabled
+    // external force (contact) -- null until contact is enabled (the contact state owns the array)
     double* d_fext = nullptr;
     hkc::Contact* contact = nullptr;
     // profiling
@@ -187,7 +187,8 @@ int comm_allgatherv_raw(hakai_ctx* c, const void* send, void* recv, const size_t
 int comm_allreduce_min_u64(hakai_ctx* c, const void* send, void* recv, size_t count);
 bool comm_is_rccl(const hakai_ctx* c);
 hakai_ctx* comm_peer_ctx(hakai_ctx* c, int q);                          // in-process group member q
-// Contact (no-ops without hakai_set_contact).
+// Contact (no-ops without hakai_set_contact): hakai_contact.hip; the multi-GPU phases, contact_step_b,
+// contact_post_step and contact_exchange_retry: hakai_contact_xr.hip.
 void contact_destroy(hakai_ctx* c);
 int contact_state_reset(hakai_ctx* c, const double* velo0_host);
 int contact_step(hakai_ctx* c, double t, double d_time);  // one GPU: contact force of step t -> d_fext

@@ -1,7 +1,7 @@
 """Contact launch fusions (hakai_contact.hip): the binning and the triangle prefilter as one launch
 (k_ct_binfilter; tuning contact_fuse_binfilter) give the same run as two launches, bit for bit,
-with deletions, self-contact and graphs (the multi-GPU insert + prefilter fusion, k_xr_insfilter,
-is checked in test_gpu_multirank.py)."""
+with deletions, self-contact and graphs (the multi-GPU insert + prefilter fusion, k_xr_insfilter
+in hakai_contact_xr.hip, is checked in test_gpu_multirank.py)."""
 import numpy as np
 import pytest
 

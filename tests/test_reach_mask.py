@@ -1,6 +1,6 @@
 """reach_mask (hakai-fem_amd/csrc/hakai_contact_cells.hpp), the one approximate filter of the contact
 search, against its defining property. The function under test is the kernel's own: this file
-compiles the header hakai_contact.hip includes with a host compiler (no contraction, as the kernel
+compiles the header the contact kernels include with a host compiler (no contraction, as the kernel
 file is built); the reference side is a plain numpy restatement of the reference's two tests and
 never calls the header.
 

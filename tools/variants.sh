@@ -15,6 +15,6 @@ wait
 for o in build/variants/*.o; do
   name=$(basename $o .o)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o lib/variants/$name.so $o build/hakai_capi.o build/hakai_comm.o \
-    build/hakai_contact.o build/hakai_host.o build/hakai_vtk.o -L/opt/rocm/lib -lrccl -lamdhip64 -pthread
+    build/hakai_contact.o build/hakai_contact_xr.o build/hakai_contact_plan.o build/hakai_own_plan.o build/hakai_host.o build/hakai_vtk.o -L/opt/rocm/lib -lrccl -lamdhip64 -pthread
 done
 ls -la lib/variants
