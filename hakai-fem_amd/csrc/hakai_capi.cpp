@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/hakai_hip.h"
+#include "hakai_history.hpp"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
 #include "hakai_own_plan.hpp"
@@ -403,6 +404,7 @@ int hakai_destroy(hakai_ctx* c) {
     prof_harvest(c);
     hkc::graph_free(c);
     dfree(c->d_tstep);
+    hkc::history_destroy(c);
     hkc::comm_destroy(c);
     hkc::free_model(c);
     hkc::free_bc(c);
@@ -437,6 +439,7 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
                     "(max %lld); split the mesh over ranks", (long long)nNode, (long long)(((int64_t)1 << 32) / 24 - 1));
     HIPCHK(hipSetDevice(c->device));
     (void)hipStreamSynchronize(c->stream);
+    hkc::history_destroy(c);  // its buffers are sized for the previous mesh: enable again
     hkc::free_model(c);
     // BC tables are sized for the previous mesh (the fused-BC per-dof table has 3nN entries): a new
     // model starts without BCs until hakai_set_bc runs again
@@ -548,7 +551,7 @@ int hakai_set_bc(hakai_ctx* c, const hakai_bc_t* bc) {
     (void)hipStreamSynchronize(c->stream);
     hkc::free_bc(c);
     const int G = bc->n_groups;
-    if (G <= 0) return 0;
+    if (G <= 0) return hkc::history_bc_changed(c);
     // Resolve in-order overwrites: final writer of each dof (v2/HAKAI_j.jl:585-617).
     std::map<long long, std::pair<int, double>> last;
     for (int g = 0; g < G; ++g) {
@@ -605,7 +608,7 @@ int hakai_set_bc(hakai_ctx* c, const hakai_bc_t* bc) {
         HIPCHK(hipMemcpyAsync(c->d_bc_of_node, of.data(), of.size() * sizeof(int), hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return hkc::history_bc_changed(c);
 }
 
 int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const double* ic_values, double d_time) {
@@ -643,6 +646,7 @@ int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const 
     }
     c->state_ok = true;
     if (int r = hkc::contact_state_reset(c, c->h_velo0.data())) return r;
+    if (int r = hkc::history_restart(c)) return r;
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
@@ -731,6 +735,7 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
     c->fe_ok = c->triax_ok = true;
     hkc::comm_reset(c);
     c->state_ok = true;
+    if (int r = hkc::history_restart(c)) return r;
     if (c->contact) {
         if (int r = hkc::contact_state_reset(c, c->h_velo0.empty() ? nullptr : c->h_velo0.data())) return r;
         HIPCHK(hipStreamSynchronize(s));
@@ -992,6 +997,7 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
     }
     rc = hkc::comm_pre_nodal(c);
     if (rc) return rc;
+    if (c->hist && (rc = hkc::history_seed(c, na, s))) return rc;  // first step after a (re)start
     hkc::prof_begin(c, HAKAI_K_NODAL, &ep);
     HIPCHK(hk::launch_nodal(na, s));
     hkc::prof_end(c, &ep);
@@ -1004,6 +1010,8 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
         HIPCHK(hk::launch_bc(ba, s));
         hkc::prof_end(c, &ep);
     }
+    // history output: this step's sums, from the Q the nodal update consumed (still intact)
+    if (c->hist && (rc = hkc::history_step(c, na, t, c->g_trd, s))) return rc;
     c->cur = 1 - c->cur;  // disp <- disp_new, disp_pre <- disp (:626-627)
     c->q_from_buf = false;
     // element update (:662-667) + triaxiality (:677) + ductile deletion (:684-764)
@@ -1051,6 +1059,7 @@ static bool graph_eligible(const hakai_ctx* c, double t) {
     // (owner-computed assembly: only once the previous step left its sums, so every captured nodal
     // update reads them)
     return c->graph && !c->comm && !c->prof && !c->q_from_buf && c->nE > 0 && hkc::contact_graph_ok(c, t) &&
+           !hkc::history_needs_seed(c) &&
            c->own_valid == own_use(const_cast<hakai_ctx*>(c));
 }
 
@@ -1400,6 +1409,11 @@ int hakai_set_tuning(hakai_ctx* c, const char* key, int64_t value) {
     if (!std::strcmp(key, "graph")) {
         if (value < 0 || value > 1024 || (value & 1)) return fail(HAKAI_ERR_ARG, "graph must be 0 or an even step count <= 1024");
         c->graph = (int)value;
+        return 0;
+    }
+    if (!std::strcmp(key, "history_one_block")) {  // the history reduction in one launch / two
+        if (value < -1 || value > 1) return fail(HAKAI_ERR_ARG, "history_one_block must be -1 (by size), 0 or 1");
+        c->hist_one_block = (int)value;
         return 0;
     }
     if (!std::strncmp(key, "contact_", 8)) {

@@ -536,6 +536,7 @@ int hakai_comm_unique_id(uint8_t id[128]) {
 int hakai_comm_init(hakai_ctx* c, int rank, int nranks, const uint8_t id[128]) {
     if (c) hkc::graph_invalidate(c);  // captured steps may hold stale buffers or settings
     if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(HAKAI_ERR_ARG, "comm_init: bad args");
+    if (c->hist) return fail(HAKAI_ERR_STATE, "comm_init: history output is enabled (one GPU only); disable it first");
     HIPCHK(hipSetDevice(c->device));
     hkc::comm_destroy(c);
     hkc::Comm* m = new hkc::Comm();
@@ -554,6 +555,8 @@ int hakai_comm_init(hakai_ctx* c, int rank, int nranks, const uint8_t id[128]) {
 int hakai_comm_init_local(hakai_ctx* c, int rank, int nranks, int64_t group_key) {
     if (c) hkc::graph_invalidate(c);  // captured steps may hold stale buffers or settings
     if (!c || nranks < 1 || rank < 0 || rank >= nranks) return fail(HAKAI_ERR_ARG, "comm_init_local: bad args");
+    if (c->hist)
+        return fail(HAKAI_ERR_STATE, "comm_init_local: history output is enabled (one GPU only); disable it first");
     HIPCHK(hipSetDevice(c->device));
     hkc::comm_destroy(c);
     hkc::Comm* m = new hkc::Comm();

@@ -11,6 +11,7 @@
 namespace hkc {
 struct Comm;     // multi-GPU state (hakai_comm.cpp)
 struct Contact;  // contact search state (hakai_contact_state.hpp)
+struct History;  // history output state (hakai_history.hip)
 int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 }  // namespace hkc
@@ -154,6 +155,9 @@ struct hakai_ctx {
     int own_s = 2;                     // batches per super-batch of the built lists (2, or 1)
     // multi-GPU
     hkc::Comm* comm = nullptr;
+    // history output (hakai_history_enable; hakai_history.hpp has the hooks)
+    hkc::History* hist = nullptr;
+    int hist_one_block = -1;           // tuning "history_one_block": -1 by size, 0 two launches, 1 one
 };
 
 

@@ -32,6 +32,11 @@ PD = POINTER(c_double)
 PI64 = POINTER(c_int64)
 PI32 = POINTER(c_int32)
 
+HISTORY_MAX_SETS = 15
+# the 16 values of a history record per set (hakai_history_enable), vectors as 3 components
+HISTORY_FIELDS = (("F_int", 0, 3), ("F_ext", 3, 3), ("P", 6, 3), ("KE", 9, 1), ("W_int", 10, 1), ("W_ext", 11, 1),
+                  ("W_bc", 12, 1), ("U", 13, 3))
+
 
 class MaterialT(ctypes.Structure):
     _fields_ = [("density", c_double), ("young", c_double), ("poisson", c_double),
@@ -126,6 +131,11 @@ def lib() -> ctypes.CDLL:
         "hakai_run_inp": (c_int, [c_char_p, c_char_p, c_int, c_int]),
         "hakai_graph_steps": (c_int, [c_void_p, PI64]),
         "hakai_stat": (c_int, [c_void_p, c_char_p, PI64]),
+        "hakai_history_enable": (c_int, [c_void_p, c_int32, PI64, PI64, c_int64, c_int64]),
+        "hakai_history_disable": (c_int, [c_void_p]),
+        "hakai_history_count": (c_int, [c_void_p, PI64, PI64]),
+        "hakai_history_read": (c_int, [c_void_p, c_int64, c_int64, PI64, PD, PD]),
+        "hakai_history_write_csv": (c_int, [c_char_p, c_int32, POINTER(c_char_p), c_int64, PI64, PD, c_double]),
         "hakai_vtk_writer_create": (c_int, [POINTER(c_void_p), c_char_p, c_int64, PD, c_int64, PI64, c_int]),
         "hakai_vtk_writer_submit": (c_int, [c_void_p, c_int, PI64, PD, PD, PD, PD, PD, PD, PD]),
         "hakai_vtk_writer_acquire": (c_int, [c_void_p, c_void_p]),
@@ -153,6 +163,8 @@ def exported_symbols() -> list[str]:
         "hakai_comm_init_local", "hakai_set_interface", "hakai_set_element_offset", "hakai_inp_read", "hakai_inp_free", "hakai_write_vtk", "hakai_run_inp",
         "hakai_graph_steps", "hakai_stat", "hakai_vtk_writer_create", "hakai_vtk_writer_submit", "hakai_vtk_writer_acquire", "hakai_vtk_writer_commit",
         "hakai_vtk_writer_wait", "hakai_vtk_writer_destroy",
+        "hakai_history_enable", "hakai_history_disable", "hakai_history_count", "hakai_history_read",
+        "hakai_history_write_csv",
     ]
 
 

@@ -177,6 +177,10 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
     if verbose and rank == 0:
         print(f"readInpFile:{fname}\nnNode:{glob.nNode}\nnElement:{glob.nElement}\ncontact_flag:{glob.contact_flag}")
         print(f"mass_scaling:{glob.mass_scaling:g}\ntime_num:{time_num:g}\nranks:{world}")
+    if rank == 0 and os.environ.get("HAKAI_HISTORY"):
+        # history output is one-GPU only (hakai_history_enable refuses a rank with a communicator)
+        print("HAKAI_HISTORY is ignored by the N-GPU driver: history output needs the one-GPU driver (hakai.hakai)",
+              file=sys.stderr)
     out = _Output(glob, gdiag, device, out_dir) if rank == 0 else None
 
     def output(idx):

@@ -203,6 +203,49 @@ class Solver:
         check(self.L.hakai_graph_steps(self.ctx, ctypes.byref(n)))
         return n.value
 
+    # -- history output --------------------------------------------------------------------------
+    def history_enable(self, sets=(), stride: int = 1, capacity: int = 1 << 16):
+        """Per-step sums over node sets (hakai_history_enable): `sets` is a list of 1-based node id
+        arrays (at most 15; set 0, every node, is always there). A record is kept every `stride`
+        states, the newest `capacity` of them."""
+        sets = [np.ascontiguousarray(s, np.int64).ravel() for s in sets]
+        off = np.zeros(len(sets) + 1, np.int64)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        nodes = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), np.int64)
+        check(self.L.hakai_history_enable(self.ctx, len(sets), ptr(off, I64), ptr(nodes, I64), int(stride),
+                                          int(capacity)))
+        self._history_sets = len(sets) + 1
+
+    def history_disable(self):
+        check(self.L.hakai_history_disable(self.ctx))
+
+    def history_count(self) -> tuple[int, int]:
+        """(records written since the last (re)start, how many of the newest are still held)."""
+        nw, nh = I64(0), I64(0)
+        check(self.L.hakai_history_count(self.ctx, ctypes.byref(nw), ctypes.byref(nh)))
+        return nw.value, nh.value
+
+    def history(self, first: int | None = None, n: int | None = None) -> dict:
+        """The held records (or records [first, first+n) counted from the (re)start): ``steps`` (n,),
+        ``values`` (n, sets, 16), ``ke_seed`` (sets,) and one array per field of
+        ``_abi.HISTORY_FIELDS`` -- (n, sets, 3) for F_int, F_ext, P, U; (n, sets) for KE, W_int,
+        W_ext, W_bc."""
+        from ._abi import HISTORY_FIELDS
+        nw, nh = self.history_count()
+        if first is None:
+            first = nw - nh
+        if n is None:
+            n = nw - first
+        S = self._history_sets
+        steps = np.zeros(max(n, 0), np.int64)
+        values = np.zeros((max(n, 0), S, 16))
+        ke = np.zeros(S)
+        check(self.L.hakai_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values), ptr(ke)))
+        out = dict(steps=steps, values=values, ke_seed=ke)
+        for name, lo, w in HISTORY_FIELDS:
+            out[name] = values[:, :, lo:lo + w] if w > 1 else values[:, :, lo]
+        return out
+
     # -- multi-GPU ---------------------------------------------------------------------------------
     def comm_init(self, rank: int, nranks: int, uid: bytes):
         buf = (ctypes.c_uint8 * 128).from_buffer_copy(uid)
@@ -289,6 +332,29 @@ def cal_triax_stress(integ_stress, integ_triax_stress, device: int = 0):
     check(lib().hakai_triax_stress(device, st.shape[0], ptr(st), ptr(integ_triax_stress)))
 
 
+def write_history_csv(path: str, set_names, steps, values, d_time: float):
+    """History records as CSV (hakai_history_write_csv): values (n, sets, 16), set 0's name first."""
+    steps = np.ascontiguousarray(steps, np.int64)
+    values = np.ascontiguousarray(values, np.float64)
+    names = (ctypes.c_char_p * len(set_names))(*[str(s).encode() for s in set_names])
+    assert values.shape == (len(steps), len(set_names), 16), values.shape
+    check(lib().hakai_history_write_csv(str(path).encode(), len(set_names), names, len(steps), ptr(steps, I64),
+                                        ptr(values), float(d_time)))
+
+
+def read_history_csv(path: str) -> dict:
+    """A history.csv back as dict(sets, steps, time, values (n, sets, 16)): the same doubles."""
+    with open(path) as fh:
+        head = fh.readline().strip().split(",")
+        rows = [ln.strip().split(",") for ln in fh if ln.strip()]
+    sets = [h[:-len("_F_int_x")] for h in head[2::16]]
+    steps = np.array([int(r[0]) for r in rows], np.int64)
+    time = np.array([float(r[1]) for r in rows])
+    values = np.array([[float(x) for x in r[2:]] for r in rows]).reshape(len(rows), len(sets), 16)
+    return dict(sets=sets, steps=steps, time=time, values=values)
+
+
 def hakai(fname: str, out_dir: str = "temp", device: int = 0, verbose: bool = True):
-    """HAKAI(fname) (v2/HAKAI_j.jl:81): run the deck on the GPU and write out_dir/file%03d.vtk."""
+    """HAKAI(fname) (v2/HAKAI_j.jl:81): run the deck on the GPU and write out_dir/file%03d.vtk.
+    Env HAKAI_HISTORY=<stride> also writes out_dir/history.csv (hakai_run_inp)."""
     check(lib().hakai_run_inp(str(fname).encode(), str(out_dir).encode(), device, int(verbose)))

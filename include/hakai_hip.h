@@ -193,6 +193,8 @@ int hakai_profile_read(hakai_ctx* ctx, int kernel, double* total_ms, int64_t* la
  *   "nodal_padded"      0: CSR force gather instead of the padded [nN][8] table;
  *   "fuse_bc"           1 (default): one GPU, <= 2^18 nodes: the nodal kernel applies the BCs;
  *   "graph"             steps per captured hipGraph (even, default 16; 0 = stream mode);
+ *   "history_one_block" history output's reduction: -1 (default) one launch up to 2048 nodes, two
+ *                       above; 0: two launches; 1: one (the same bits either way);
  *   "contact_event_cap", "contact_candidate_cap", "contact_full_rebuild": contact buffers and
  *                       rebuild policy;
  *   "contact_exchange_deletions", "contact_exchange_bins", "contact_exchange_events": multi-GPU
@@ -206,6 +208,54 @@ int hakai_profile_read(hakai_ctx* ctx, int kernel, double* total_ms, int64_t* la
  *                       same, each phase enqueued behind a fixed ≈0.3 ms sleep kernel so it runs
  *                       back to back on the GPU instead of at the host's enqueue pace. */
 int hakai_set_tuning(hakai_ctx* ctx, const char* key, int64_t value);
+
+/* ---- history output: per-step sums over node sets, computed on the device inside the step ---- */
+/* With history enabled every hakai_step (captured graphs included) sums, after its nodal update
+ * and BCs, 16 values over each node set -- set 0 is every node, sets 1..n_sets the caller's; a node
+ * may be in several. Notation: u_k the displacement after k steps, Q_k / f_k the internal / contact
+ * force assembled from u_k (what step k+1's nodal update consumes), du_k = u_k - u_{k-1},
+ * c_k = (du_{k+1} + du_k) / 2. Step t = k+1 sums, per set:
+ *    0-2  F_int[c]  Q_k (the reaction force on a clamped set)
+ *    3-5  F_ext[c]  f_k (0 without contact)
+ *    6-8  P[c]      m du_{k+1} / dt
+ *    9    KE        1/2 m sum_c (du_{k+1} / dt)^2 (the velocity a download after this step reports)
+ *   10    W_int     accumulated since the (re)start: += sum_c Q_k c_k
+ *   11    W_ext     accumulated: += sum_c f_k c_k
+ *   12    W_bc      accumulated, prescribed dofs only: += r_k c_k, the constraint force
+ *                   r_k = m (du_{k+1} - du_k) / dt^2 + Q_k - f_k
+ *   13-15 U[c]      u_k (a sum: divide by the set's size for the mean)
+ * For set 0, KE - KE_seed + W_int - W_ext - W_bc = 0 up to rounding: an identity of the central
+ * difference update (DESIGN.md "History output"), so its drift is a check of the whole step. The
+ * works accumulate every step; a record (k, then the values of every set) is kept when
+ * k % stride == 0, in a ring of the newest `capacity` records. Records describe states 0 .. N-1 of
+ * an N-step run: the Q of the state after the last step is never consumed. The (re)start is the
+ * enable call and every hakai_reset_state / hakai_upload_state: the count returns to 0, the works to
+ * 0, and the first step afterwards stores KE_seed = sum 1/2 m ((disp - disp_pre) / d_time)^2 with
+ * its d_time. A step a contact overflow poisoned leaves no record and accumulates nothing. The sums
+ * are taken in a fixed tree over the node numbers: the same bits for every tuning setting and
+ * launch form. hakai_upload_model disables history; hakai_set_bc keeps it.
+ * Not supported on a context with a communicator (hakai_comm_init / hakai_comm_init_local):
+ * hakai_history_enable returns HAKAI_ERR_STATE there, and both comm calls refuse a context with
+ * history enabled. Tuning "history_one_block" (-1 default: by mesh size; 0; 1) picks the reduction's
+ * launch form: one workgroup in one launch, or chunk partials and a combining launch. */
+#define HAKAI_HISTORY_MAX_SETS 15
+#define HAKAI_HISTORY_FIELDS 16
+/* set_off[n_sets+1] into set_nodes (1-based node ids; duplicates within a set are an error; an
+ * empty set is allowed and records zeros). Bad arguments (a node id out of range, more than 15
+ * sets, stride < 1, capacity < 1) return HAKAI_ERR_ARG and change nothing. */
+int hakai_history_enable(hakai_ctx* ctx, int32_t n_sets, const int64_t* set_off, const int64_t* set_nodes,
+                         int64_t stride, int64_t capacity);
+int hakai_history_disable(hakai_ctx* ctx);
+/* records written since the last (re)start, and how many of the newest the ring still holds */
+int hakai_history_count(hakai_ctx* ctx, int64_t* n_written, int64_t* n_held);
+/* syncs; records [first, first+n) counted from the (re)start, must still be held (else
+ * HAKAI_ERR_ARG); steps[n], values[n][(n_sets+1)][16], ke_seed[n_sets+1] (any pointer may be NULL) */
+int hakai_history_read(hakai_ctx* ctx, int64_t first, int64_t n, int64_t* steps, double* values, double* ke_seed);
+/* Host helper (no GPU): n records as CSV -- one header line step,time,<set>_<field>,... (fields
+ * F_int_x .. U_z in record order, set_names[n_names] with set 0 first), one line per record with
+ * time = step * d_time and every value as %.17g (parses back to the same double). */
+int hakai_history_write_csv(const char* path, int32_t n_names, const char* const* set_names, int64_t n,
+                            const int64_t* steps, const double* values, double d_time);
 
 /* ---- contact: all-exterior instance-vs-instance penalty contact --------- */
 /* Enables contact for the uploaded model: contact_flag as readInpFile sets it (1 = *Contact,
@@ -359,7 +409,11 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
 
 /* HAKAI(fname) (v2/HAKAI_j.jl:81-978): read, set up, run the whole step loop on `device`, write
  * out_dir/file000.vtk .. file100.vtk every floor(time_num/100) steps. verbose=1 prints the
- * reference's progress lines. Returns 0 or <0. */
+ * reference's progress lines. Returns 0 or <0.
+ * Env HAKAI_HISTORY=<stride> (>= 1) enables history output for the run and writes
+ * out_dir/history.csv (hakai_history_write_csv) at the end: set "all", then "inst<i>" per instance,
+ * then "bc<g>" per *Boundary group (the nodes of its dofs), 15 sets at most (verbose: the ones left
+ * out are named on stderr); the ring holds the whole run. Without the variable nothing changes. */
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose);
 
 #ifdef __cplusplus

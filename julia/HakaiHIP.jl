@@ -186,6 +186,38 @@ end
 set_tuning(c::Ctx, key::AbstractString, value::Integer) =
     check(ccall((:hakai_set_tuning, lib), Cint, (Ptr{Cvoid}, Cstring, Int64), c.p, key, value))
 
+# History output (hakai_history_enable, include/hakai_hip.h): per-step sums over node sets, kept on
+# the device in a ring of the newest `capacity` records, one every `stride` states. sets: vectors of
+# 1-based node ids (at most 15); set 0, every node, is always there.
+const HISTORY_FIELDS = (:F_int_x, :F_int_y, :F_int_z, :F_ext_x, :F_ext_y, :F_ext_z, :P_x, :P_y, :P_z, :KE,
+                        :W_int, :W_ext, :W_bc, :U_x, :U_y, :U_z)
+function history_enable(c::Ctx, sets::Vector{<:AbstractVector{<:Integer}}; stride::Integer = 1,
+                        capacity::Integer = 1 << 16)
+    off = Int64[0]; nodes = Int64[]
+    for s in sets
+        append!(nodes, s); push!(off, length(nodes))
+    end
+    check(ccall((:hakai_history_enable, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Int64, Int64),
+                c.p, length(sets), off, nodes, stride, capacity))
+    return length(sets) + 1
+end
+history_disable(c::Ctx) = check(ccall((:hakai_history_disable, lib), Cint, (Ptr{Cvoid},), c.p))
+# (records written since the last (re)start, how many of the newest the ring still holds)
+function history_count(c::Ctx)
+    nw = Ref{Int64}(0); nh = Ref{Int64}(0)
+    check(ccall((:hakai_history_count, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c.p, nw, nh))
+    return nw[], nh[]
+end
+# the held records of a history with n_total sets (history_enable's return value): steps[n],
+# values[16, n_total, n] (field, set, record; HISTORY_FIELDS), ke_seed[n_total]
+function history(c::Ctx, n_total::Integer)
+    nw, nh = history_count(c)
+    steps = zeros(Int64, nh); values = zeros(Float64, 16, n_total, nh); ke_seed = zeros(Float64, n_total)
+    check(ccall((:hakai_history_read, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                c.p, nw - nh, nh, steps, values, ke_seed))
+    return steps, values, ke_seed
+end
+
 # cal_node_stress_strain (v2/HAKAI_j.jl:3408-3486) on the device -> the fields of NodeDataType
 # (node_stress / node_strain nNode x 6 like the reference; node_plastic_strain stays zero, :450)
 function node_stress_strain(c::Ctx, nNode::Integer)

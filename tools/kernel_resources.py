@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "hakai-fem_amd")
 FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-munsafe-fp-atomics"]
 CONTRACT = {"hakai_kernels.hip": "-ffp-contract=on", "hakai_contact.hip": "-ffp-contract=off",
-            "hakai_contact_xr.hip": "-ffp-contract=off"}  # as the Makefile
+            "hakai_contact_xr.hip": "-ffp-contract=off", "hakai_history.hip": "-ffp-contract=off"}  # as the Makefile
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
           "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "lds_static_bytes", "Dynamic Stack": "dynamic_stack"}
