@@ -1002,7 +1002,8 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
     HIPCHK(hk::launch_nodal(na, s));
     hkc::prof_end(c, &ep);
     // multi-GPU: interface nodes are redone with the cross-rank assembled Q
-    rc = hkc::comm_post_nodal(c, d_time);
+    hkc::CommFix fix;  // what the fix read: the history hook forms the same Q at the nodes this rank owns
+    rc = hkc::comm_post_nodal(c, d_time, &fix);
     if (rc) return rc;
     // boundary conditions (:585-617)
     if (c->nbc > 0 && !fuse_bc) {
@@ -1011,7 +1012,7 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
         hkc::prof_end(c, &ep);
     }
     // history output: this step's sums, from the Q the nodal update consumed (still intact)
-    if (c->hist && (rc = hkc::history_step(c, na, t, c->g_trd, s))) return rc;
+    if (c->hist && (rc = hkc::history_step(c, na, fix, t, c->g_trd, s))) return rc;
     c->cur = 1 - c->cur;  // disp <- disp_new, disp_pre <- disp (:626-627)
     c->q_from_buf = false;
     // element update (:662-667) + triaxiality (:677) + ductile deletion (:684-764)

@@ -46,7 +46,9 @@ struct Comm {
     double* d_dn_sendC[2] = {nullptr, nullptr};  // [n_dn][nslot][3]
     double* d_dn_recvP = nullptr;                // [n_dn][3]
     double* d_saved = nullptr;                   // u_pre of interface nodes [n_up+n_dn][3]
-    std::vector<int> h_dn;                       // host copy of d_dn (owner-computed assembly)
+    std::vector<int> h_dn;                       // host copy of d_dn (owner-computed assembly, history)
+    std::vector<int> h_up;                       // host copy of d_up (history: the nodes whose Q the fix forms)
+    bool iface_set = false;                      // hakai_set_interface has run (an empty interface counts)
     bool pending = false;
     int pending_par = 0;
     // collectives of the multi-GPU contact (hakai_contact_xr.hip) on cs, handed over by events
@@ -432,6 +434,8 @@ void comm_rollback(hakai_ctx* c, bool had_good, long long last_good, bool pendin
 }
 
 const std::vector<int>* comm_dn_nodes(const hakai_ctx* c) { return c->comm ? &c->comm->h_dn : nullptr; }
+const std::vector<int>* comm_up_nodes(const hakai_ctx* c) { return c->comm ? &c->comm->h_up : nullptr; }
+bool comm_iface_set(const hakai_ctx* c) { return c->comm && c->comm->iface_set; }
 
 int comm_pre_nodal(hakai_ctx* c) {
     Comm* m = c->comm;
@@ -443,11 +447,18 @@ int comm_pre_nodal(hakai_ctx* c) {
     return 0;
 }
 
-int comm_post_nodal(hakai_ctx* c, double d_time) {
+int comm_post_nodal(hakai_ctx* c, double d_time, CommFix* fix) {
     Comm* m = c->comm;
     if (!m || m->n_up + m->n_dn == 0 || !m->pending) return 0;
     m->pending = false;
     const int par = m->pending_par;
+    if (fix && !c->q_from_buf) {  // one of the two fix kernels below runs, on these buffers
+        fix->ran = true;
+        fix->n_up = m->n_up;
+        fix->nslot = m->nslot;
+        fix->up_sendP = m->d_up_sendP[par];
+        fix->up_recvC = m->d_up_recvC;
+    }
     EventPair ep;
     prof_begin(c, HAKAI_K_EXCHANGE, &ep);
     if (m->mode == 0) {
@@ -536,7 +547,9 @@ int hakai_comm_unique_id(uint8_t id[128]) {
 int hakai_comm_init(hakai_ctx* c, int rank, int nranks, const uint8_t id[128]) {
     if (c) hkc::graph_invalidate(c);  // captured steps may hold stale buffers or settings
     if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(HAKAI_ERR_ARG, "comm_init: bad args");
-    if (c->hist) return fail(HAKAI_ERR_STATE, "comm_init: history output is enabled (one GPU only); disable it first");
+    if (c->hist)
+        return fail(HAKAI_ERR_STATE, "comm_init: history output is enabled (its node ownership comes from the "
+                    "interface); disable it first");
     HIPCHK(hipSetDevice(c->device));
     hkc::comm_destroy(c);
     hkc::Comm* m = new hkc::Comm();
@@ -556,7 +569,8 @@ int hakai_comm_init_local(hakai_ctx* c, int rank, int nranks, int64_t group_key)
     if (c) hkc::graph_invalidate(c);  // captured steps may hold stale buffers or settings
     if (!c || nranks < 1 || rank < 0 || rank >= nranks) return fail(HAKAI_ERR_ARG, "comm_init_local: bad args");
     if (c->hist)
-        return fail(HAKAI_ERR_STATE, "comm_init_local: history output is enabled (one GPU only); disable it first");
+        return fail(HAKAI_ERR_STATE, "comm_init_local: history output is enabled (its node ownership comes from "
+                    "the interface); disable it first");
     HIPCHK(hipSetDevice(c->device));
     hkc::comm_destroy(c);
     hkc::Comm* m = new hkc::Comm();
@@ -599,6 +613,9 @@ int hakai_set_interface(hakai_ctx* c, int64_t n_shared, const int64_t* local_nod
     hkc::Comm* m = c->comm;
     if (!m) return fail(HAKAI_ERR_STATE, "set_interface before comm_init");
     if (!c->model_ok) return fail(HAKAI_ERR_STATE, "set_interface before upload_model");
+    if (c->hist)
+        return fail(HAKAI_ERR_STATE, "set_interface: history output is enabled (its node ownership comes from the "
+                    "interface); disable it first");
     if (n_shared < 0 || (n_shared > 0 && (!local_node || !rank_lo || !rank_hi)))
         return fail(HAKAI_ERR_ARG, "set_interface: bad arrays");
     HIPCHK(hipSetDevice(c->device));
@@ -640,6 +657,8 @@ int hakai_set_interface(hakai_ctx* c, int64_t n_shared, const int64_t* local_nod
     m->n_up = (int)up.size();
     m->n_dn = (int)dn.size();
     m->h_dn = dn;
+    m->h_up = up;
+    m->iface_set = true;
     c->own_built_g = -1;  // owner-assembly lists export every dn node's contributions: rebuilt
     c->own_for_g0 = -1;
     c->own_valid = false;

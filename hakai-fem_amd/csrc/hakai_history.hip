@@ -14,6 +14,10 @@
 // pairs; a subtree without a right sibling moves up unchanged), so its bits depend on the node
 // numbering and the sets alone, not on the launch form or the grid.
 // Compiled without contraction: Q is formed with k_nodal's additions in k_nodal's order.
+// On a rank (a context with a communicator) the same tree runs over the rank's local numbering and
+// over the nodes it owns: a node shared with the rank below counts nowhere, and at a node shared
+// with the rank above Q is the cross-rank sum the interface fix consumed (hist_q_up). Nothing is
+// exchanged; hakai_history_combine (host) adds the ranks' records in rank order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,14 +46,25 @@ constexpr int kHF = HAKAI_HISTORY_FIELDS;               // values per set
 constexpr int kHMaxS = HAKAI_HISTORY_MAX_SETS + 1;      // set 0 (every node) + the caller's
 constexpr int kHDepthPart = 4;                          // open subtrees while a group's chunks are combined
 constexpr int kHDepth = 24;                             // ... while up to 2^23 group partials are
+constexpr unsigned kHNotOwned = 0x8000u;                // HistArgs::set: bits 0-14 are the caller's sets
+constexpr unsigned kHUp = 0x80u;                        // HistArgs::presc: bits 0-2 are the dofs
 static_assert(kHF == 16 && kHMaxS * kHF <= kHB, "one thread per (set, field) in a block");
+static_assert(HAKAI_HISTORY_MAX_SETS <= 15, "the not-owned mark takes bit 15 of the set mask");
 static_assert((1 << (kHDepthPart - 1)) >= kHGroup, "stack of the group's chunk tree");
 
 struct HistArgs {
     NodalArgs na;               // as launch_nodal took it: u = u_k, u_pre_out = u_{k+1} (seed: u_{k-1})
     double* du_prev;            // [3nN] u_k - u_{k-1}; the step stores u_{k+1} - u_k
-    const unsigned short* set;  // [nN] bit s-1: the node is in set s (set 0 is every node)
-    const unsigned char* presc; // [nN] bit c: dof c of the node is prescribed
+    const unsigned short* set;  // [nN] bit s-1: the node is in set s (set 0 is every node);
+                                // kHNotOwned: a rank's node that the rank below owns (in no set, set 0 included)
+    const unsigned char* presc; // [nN] bit c: dof c of the node is prescribed; kHUp: shared with the rank above
+    // a rank's interface with the rank above (null / 0 without one): the nodes ascending, each with its
+    // position in the exchange buffers; up_sendP is null in a step whose nodal update no fix followed
+    const int* up_node;         // [n_up]
+    const int* up_slot;         // [n_up]
+    const double* up_sendP;     // [n_up][3]
+    const double* up_recvC;     // [n_up][nslot][3]
+    int n_up, nslot;
     int S;                      // sets, set 0 included
     int seed;                   // 1: the (re)start pass (du_prev, KE_seed, accumulators and count zeroed)
     double* gp;                 // [ngroups][S][16] group partials
@@ -132,6 +147,34 @@ __device__ __forceinline__ void hist_q(const NodalArgs& a, long long n, double Q
     Q[2] = Q2;
 }
 
+// Q_k of a node shared with the rank above, in a step whose nodal update the interface fix
+// followed: the cross-rank sum the fix consumed, k_fix's (k_fix_own's) additions in their order --
+// this rank's partial sum, then the upper rank's contributions one by one. The node's position in
+// the exchange buffers comes from a search of the ascending node list (interface nodes only take
+// this branch). False if the node is not in the list (the caller then takes the nodal source).
+__device__ __forceinline__ bool hist_q_up(const HistArgs& h, long long n, double Q[3]) {
+#pragma clang fp contract(off)
+    int lo = 0, hi = h.n_up;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (h.up_node[mid] < n) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= h.n_up || h.up_node[lo] != n) return false;
+    const int j = h.up_slot[lo];
+    double Q0 = h.up_sendP[3 * j + 0], Q1 = h.up_sendP[3 * j + 1], Q2 = h.up_sendP[3 * j + 2];
+    const double* r = h.up_recvC + (long long)3 * h.nslot * j;
+    for (int s = 0; s < h.nslot; ++s) {
+        Q0 += r[3 * s + 0];
+        Q1 += r[3 * s + 1];
+        Q2 += r[3 * s + 2];
+    }
+    Q[0] = Q0;
+    Q[1] = Q1;
+    Q[2] = Q2;
+    return true;
+}
+
 // The 16 terms of node n (field order of the header) and its new du_prev.
 template <int MODE>
 __device__ __forceinline__ void hist_node(const HistArgs& h, long long n, double val[kHF]) {
@@ -156,8 +199,8 @@ __device__ __forceinline__ void hist_node(const HistArgs& h, long long n, double
         return;
     }
     double Q[3];
-    hist_q<MODE>(a, n, Q);
     const unsigned pm = h.presc[n];
+    if (!((pm & kHUp) && h.up_sendP && hist_q_up(h, n, Q))) hist_q<MODE>(a, n, Q);
     double v[3], wi[3], we[3], wb = 0.0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -223,8 +266,13 @@ __device__ __forceinline__ void hist_group(const HistArgs& h, long long g, doubl
         for (int f = 0; f < kHF; ++f) val[f] = 0.0;
         unsigned member = 0;
         if (n < h.na.nN) {
-            hist_node<MODE>(h, n, val);
-            member = 1u | ((unsigned)h.set[n] << 1);
+            // a node the rank below owns counts nowhere, like a lane past nN: a wave of them has
+            // nothing to load, and every set's ballot below skips its sums
+            const unsigned sv = h.set[n];
+            if (!(sv & kHNotOwned)) {
+                hist_node<MODE>(h, n, val);
+                member = 1u | (sv << 1);
+            }
         }
         for (int s = 0; s < h.S; ++s) {
             const bool in = (member >> s) & 1u;
@@ -385,8 +433,11 @@ struct History {
     double* d_ring = nullptr;
     unsigned long long* d_count = nullptr;
     double* d_gp = nullptr;
+    int n_up = 0;                // a rank: its nodes shared with the rank above, ascending, and their
+    int* d_up_node = nullptr;    // positions in the exchange buffers (hist_q_up)
+    int* d_up_slot = nullptr;
     void free() {
-        void* p[] = {d_du_prev, d_set, d_presc, d_acc, d_ke, d_ring, d_count, d_gp};
+        void* p[] = {d_du_prev, d_set, d_presc, d_acc, d_ke, d_ring, d_count, d_gp, d_up_node, d_up_slot};
         for (void* q : p)
             if (q) (void)hipFree(q);
     }
@@ -420,12 +471,14 @@ int history_bc_changed(hakai_ctx* c) {
     if (c->nbc > 0) HIPCHK(hipMemcpy(dof.data(), c->d_bc_dof, dof.size() * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<unsigned char> pm((size_t)c->nN, 0);
     for (int d : dof) pm[(size_t)d / 3] |= (unsigned char)(1u << (d % 3));
+    if (const std::vector<int>* up = comm_up_nodes(c))  // a rank: the nodes whose Q the interface fix forms
+        for (int n : *up) pm[(size_t)n] |= (unsigned char)hk::kHUp;
     HIPCHK(hipMemcpyAsync(H->d_presc, pm.data(), pm.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
-static hk::HistArgs hist_args(hakai_ctx* c, const hk::NodalArgs& na) {
+static hk::HistArgs hist_args(hakai_ctx* c, const hk::NodalArgs& na, const CommFix* fix = nullptr) {
     const History* H = c->hist;
     hk::HistArgs h;
     std::memset(&h, 0, sizeof h);
@@ -443,6 +496,14 @@ static hk::HistArgs hist_args(hakai_ctx* c, const hk::NodalArgs& na) {
     h.count = H->d_count;
     h.stride = H->stride;
     h.cap = H->cap;
+    h.up_node = H->d_up_node;
+    h.up_slot = H->d_up_slot;
+    h.n_up = H->n_up;
+    if (fix && fix->ran && fix->n_up == H->n_up && H->n_up > 0) {  // (set_interface is refused while history is on)
+        h.up_sendP = fix->up_sendP;
+        h.up_recvC = fix->up_recvC;
+        h.nslot = fix->nslot;
+    }
     return h;
 }
 
@@ -459,9 +520,12 @@ int history_seed(hakai_ctx* c, const hk::NodalArgs& na, hipStream_t s) {
     return 0;
 }
 
-int history_step(hakai_ctx* c, const hk::NodalArgs& na, double t, const double* t_rd, hipStream_t s) {
+int history_step(hakai_ctx* c, const hk::NodalArgs& na, const CommFix& fix, double t, const double* t_rd,
+                 hipStream_t s) {
     if (!c->hist) return 0;
-    hk::HistArgs h = hist_args(c, na);
+    if (fix.ran && fix.n_up != c->hist->n_up)
+        return fail(HAKAI_ERR_STATE, "history: the interface changed since history_enable");
+    hk::HistArgs h = hist_args(c, na, &fix);
     h.t = t;
     h.t_rd = t_rd;
     HIPCHK(hk::launch_history(h, hist_one_block(c), s));
@@ -476,8 +540,9 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
                          int64_t stride, int64_t capacity) {
     if (!c) return fail(HAKAI_ERR_ARG, "null");
     if (!c->model_ok) return fail(HAKAI_ERR_STATE, "history_enable before upload_model");
-    if (c->comm)
-        return fail(HAKAI_ERR_STATE, "history_enable: a context with a communicator is not supported (one GPU only)");
+    if (c->comm && !hkc::comm_iface_set(c))  // a rank's node ownership comes from its interface
+        return fail(HAKAI_ERR_STATE, "history_enable: a context with a communicator needs hakai_set_interface first "
+                    "(an empty interface counts)");
     if (n_sets < 0 || n_sets > HAKAI_HISTORY_MAX_SETS)
         return fail(HAKAI_ERR_ARG, "history_enable: %d sets (0..%d)", n_sets, HAKAI_HISTORY_MAX_SETS);
     if (n_sets > 0 && !set_off) return fail(HAKAI_ERR_ARG, "history_enable: null set_off");
@@ -500,10 +565,25 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
             set[n - 1] |= (unsigned short)(1u << s);
         }
     }
+    // a rank: the nodes shared with the rank below are that rank's (the contact search's owner rule);
+    // the nodes shared with the rank above ascending, each with its position in the exchange buffers
+    std::vector<int> up_node, up_slot;
+    if (c->comm) {
+        for (int n : *hkc::comm_dn_nodes(c)) set[(size_t)n] = (unsigned short)hk::kHNotOwned;
+        const std::vector<int>& up = *hkc::comm_up_nodes(c);
+        std::vector<int> order(up.size());
+        for (size_t j = 0; j < up.size(); ++j) order[j] = (int)j;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return up[a] < up[b]; });
+        for (int j : order) {
+            up_node.push_back(up[j]);
+            up_slot.push_back(j);
+        }
+    }
     HIPCHK(hipSetDevice(c->device));
     hkc::graph_invalidate(c);  // the captured steps change
     hkc::history_destroy(c);
     hkc::History* H = new hkc::History();
+    H->n_up = (int)up_node.size();
     H->n_sets = n_sets;
     H->stride = stride;
     H->cap = capacity;
@@ -523,6 +603,12 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
     alloc((void**)&H->d_ring, (size_t)capacity * (1 + S16) * sizeof(double));
     alloc((void**)&H->d_count, sizeof(unsigned long long));
     alloc((void**)&H->d_gp, (size_t)H->ngroups * S16 * sizeof(double));
+    if (H->n_up > 0) {
+        alloc((void**)&H->d_up_node, up_node.size() * sizeof(int));
+        alloc((void**)&H->d_up_slot, up_slot.size() * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpyAsync(H->d_up_node, up_node.data(), up_node.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(H->d_up_slot, up_slot.data(), up_slot.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(H->d_set, set.data(), nN * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {

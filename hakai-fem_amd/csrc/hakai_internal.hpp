@@ -170,10 +170,21 @@ void comm_pending_get(const hakai_ctx* c, bool* pending, int* par);
 void comm_rollback(hakai_ctx* c, bool had_good, long long last_good, bool pending, int par);
 // Multi-GPU hooks used by hakai_step (no-ops without a communicator).
 int comm_pre_nodal(hakai_ctx* c);                    // save u_pre of interface nodes
-int comm_post_nodal(hakai_ctx* c, double d_time);    // wait exchange, fix interface nodes
+// What the interface fix of a step read, for the history hook (hakai_history.hip hist_q_up forms the
+// same Q at the nodes this rank owns): ran is false in a step without a fix (first step after a
+// reset or an upload, an uploaded Q, no interface) -- the nodal kernel's own source is the Q then.
+struct CommFix {
+    bool ran = false;
+    int n_up = 0, nslot = 0;
+    const double* up_sendP = nullptr;  // [n_up][3], the parity the fix used
+    const double* up_recvC = nullptr;  // [n_up][nslot][3]
+};
+int comm_post_nodal(hakai_ctx* c, double d_time, CommFix* fix = nullptr);  // wait exchange, fix interface nodes
 int comm_post_element(hakai_ctx* c, long long step); // pack interface forces, start exchange
 bool comm_is_local(const hakai_ctx* c);              // in-process group stepped in lockstep
 const std::vector<int>* comm_dn_nodes(const hakai_ctx* c);  // nodes shared with rank-1 (or null)
+const std::vector<int>* comm_up_nodes(const hakai_ctx* c);  // nodes shared with rank+1, in exchange order (or null)
+bool comm_iface_set(const hakai_ctx* c);             // hakai_set_interface has run on this communicator
 int comm_rank(const hakai_ctx* c);
 int comm_size(const hakai_ctx* c);
 // in-process group: dst + off[q] <- src[q] (bytes[q], 8-byte aligned), all ranks in one launch on

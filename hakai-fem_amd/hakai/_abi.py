@@ -136,6 +136,8 @@ def lib() -> ctypes.CDLL:
         "hakai_history_count": (c_int, [c_void_p, PI64, PI64]),
         "hakai_history_read": (c_int, [c_void_p, c_int64, c_int64, PI64, PD, PD]),
         "hakai_history_write_csv": (c_int, [c_char_p, c_int32, POINTER(c_char_p), c_int64, PI64, PD, c_double]),
+        "hakai_history_combine": (c_int, [c_int32, c_int32, c_int64, PI64, PD, PD, PI64, PD, PD]),
+        "hakai_inp_history_sets": (c_int, [POINTER(InpModelT), PI32, PI64, PI64, c_int64, c_char_p, c_int64, PI32]),
         "hakai_vtk_writer_create": (c_int, [POINTER(c_void_p), c_char_p, c_int64, PD, c_int64, PI64, c_int]),
         "hakai_vtk_writer_submit": (c_int, [c_void_p, c_int, PI64, PD, PD, PD, PD, PD, PD, PD]),
         "hakai_vtk_writer_acquire": (c_int, [c_void_p, c_void_p]),
@@ -164,7 +166,7 @@ def exported_symbols() -> list[str]:
         "hakai_graph_steps", "hakai_stat", "hakai_vtk_writer_create", "hakai_vtk_writer_submit", "hakai_vtk_writer_acquire", "hakai_vtk_writer_commit",
         "hakai_vtk_writer_wait", "hakai_vtk_writer_destroy",
         "hakai_history_enable", "hakai_history_disable", "hakai_history_count", "hakai_history_read",
-        "hakai_history_write_csv",
+        "hakai_history_write_csv", "hakai_history_combine", "hakai_inp_history_sets",
     ]
 
 

@@ -197,6 +197,41 @@ def bar_slab(nx: int, ny: int, nz: int, rank: int, world: int, material, v_z, pe
     return local, diag, iface
 
 
+def slab_node_global(local: Model) -> np.ndarray:
+    """local_node_global (1-based) of a slab_partition / bar_slab rank: its layers are a contiguous
+    range of the global node numbers."""
+    return np.arange(1, local.nNode + 1, dtype=np.int64) + int(local.global_node_offset)
+
+
+def local_sets(sets, local_node_global) -> list:
+    """Global 1-based node sets as a rank's local 1-based ids (history_enable on a rank), through
+    the rank's local_node_global. A node two ranks share stays in the set on both: the library
+    counts it on the rank that owns it (owned_nodes). Nodes the rank does not hold drop out; the
+    order within a set follows the global set."""
+    l2g = np.asarray(local_node_global, np.int64).ravel()
+    order = np.argsort(l2g, kind="stable")
+    out = []
+    for s in sets:
+        s = np.asarray(s, np.int64).ravel()
+        if len(l2g) == 0 or len(s) == 0:
+            out.append(np.zeros(0, np.int64))
+            continue
+        pos = np.minimum(np.searchsorted(l2g, s, sorter=order), len(l2g) - 1)
+        loc = order[pos]
+        out.append(np.ascontiguousarray(loc[l2g[loc] == s] + 1, dtype=np.int64))
+    return out
+
+
+def owned_nodes(n_local: int, iface, rank: int) -> np.ndarray:
+    """Mask of the local nodes a rank owns, by the library's rule (the contact search's and the
+    history output's): a node shared by ranks lo and lo+1 belongs to lo, so a rank owns every local
+    node except those it shares with the rank below. iface = (local_node 0-based, rank_lo, rank_hi)."""
+    ln, _, hi = iface
+    own = np.ones(n_local, bool)
+    own[np.asarray(ln, np.int64)[np.asarray(hi) == rank]] = False
+    return own
+
+
 def rank_device(local_rank: int, local_world: int) -> int:
     """The HIP device of a local rank: device = local rank on a node with a GPU per rank; with fewer
     visible GPUs than local ranks, local rank mod the visible count (e.g. one visible GPU per process

@@ -57,6 +57,9 @@ class Model:
     # *Contact Pair surfaces: [((instance, elements), (instance, elements)), ...] with 1-based
     # instances and instance-local 1-based element ids; None = all-exterior contact
     contact_pairs: list | None = None
+    # read_inp: the drivers' history sets of the deck (hakai_inp_history_sets) -- (names with "all"
+    # first, [global 1-based node ids per kept set], names left out); None for a model built in code
+    history_sets: tuple | None = None
 
     def c_contact_pairs(self):
         """(n_cp, cp_instance int32[2n], cp_elem_off int64[2n+1], cp_elems int64[]) for the C ABI."""
@@ -213,7 +216,20 @@ def read_inp(path: str) -> Model:
             els = _arr(m.cp_elems, int(off[-1]), np.int64)
             cps = [tuple((int(inst[2 * k + s]), els[off[2 * k + s]:off[2 * k + s + 1]].copy()) for s in range(2))
                    for k in range(m.n_cp)]
+        # the sets HAKAI_HISTORY records, from the one definition both drivers use
+        ns, nd = ctypes.c_int32(0), ctypes.c_int32(0)
+        hoff = np.zeros(_abi.HISTORY_MAX_SETS + 1, np.int64)
+        check(L.hakai_inp_history_sets(out, ctypes.byref(ns), ptr(hoff, ctypes.c_int64), None, 0, None, 0,
+                                       ctypes.byref(nd)))
+        hnodes = np.zeros(max(int(hoff[ns.value]), 1), np.int64)
+        cap = 32 * (ns.value + nd.value + 2)
+        text = ctypes.create_string_buffer(cap)
+        check(L.hakai_inp_history_sets(out, ctypes.byref(ns), ptr(hoff, ctypes.c_int64), ptr(hnodes, ctypes.c_int64),
+                                       len(hnodes), text, cap, ctypes.byref(nd)))
+        hnames = text.value.decode().split("\n")[:-1]
+        hsets = [hnodes[hoff[s]:hoff[s + 1]].copy() for s in range(ns.value)]
         return Model(coord, elem, emat, mats, bc, ic_d, ic_v, m.d_time, m.end_time, m.mass_scaling,
-                     m.contact_flag, einst, name=str(path), contact_pairs=cps)
+                     m.contact_flag, einst, name=str(path), contact_pairs=cps,
+                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]))
     finally:
         L.hakai_inp_free(out)

@@ -12,6 +12,11 @@ their state to rank 0, which uploads it into an output context holding the whole
 node averages there (cal_node_stress_strain, :3408-3486) and writes out_dir/file%03d.vtk (:3517-3717)
 -- the same files, byte for byte, as the one-GPU driver (hakai.hakai / bin/hakai).
 
+Env HAKAI_HISTORY=<stride> also writes out_dir/history.csv, with the one-GPU driver's sets, names
+and capacity rule (hakai_inp_history_sets): every rank records the sums over the nodes it owns, the
+records travel to rank 0 once at the end of the run, and rank 0 adds them in rank order
+(hakai_history_combine). The VTK files are the same bytes with and without.
+
 `local_ranks=N` runs the same partition as an in-process group on one device (tests).
 """
 from __future__ import annotations
@@ -25,9 +30,9 @@ from dataclasses import replace
 import numpy as np
 
 from . import dist as _dist
-from ._abi import check, lib, ptr
+from ._abi import HISTORY_MAX_SETS, check, lib, ptr
 from .model import read_inp
-from .solver import Solver, State, comm_unique_id, step_group
+from .solver import Solver, State, comm_unique_id, history_combine, step_group, write_history_csv
 
 I64 = ctypes.c_int64
 
@@ -76,6 +81,41 @@ def gather_parts(tdist, group, rank: int, world: int, part: dict, metas: list, d
                 buf = t.cpu().numpy()
             arrs[k] = buf
         out.append(((l2g, e0), arrs))
+    return out
+
+
+def gather_history(tdist, group, rank: int, world: int, part: dict, device=None):
+    """Rank 0 collects every rank's history records (Solver.history() dicts) once, at the end of the
+    run: the record count, then steps, values and ke_seed as raw tensors (host tensors over gloo,
+    device tensors over the NCCL group, as gather_parts). Returns the dicts in rank order on rank 0,
+    None elsewhere."""
+    import torch
+    keys = ("steps", "values", "ke_seed")
+
+    def send(a):
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        tdist.send(t if device is None else t.to(device), 0, group=group)
+
+    def recv(r, shape, dt):
+        if device is None:
+            buf = np.empty(shape, dt)
+            tdist.recv(torch.from_numpy(buf), r, group=group)
+            return buf
+        t = torch.empty(shape, dtype=torch.float64 if dt == np.float64 else torch.int64, device=device)
+        tdist.recv(t, r, group=group)
+        return t.cpu().numpy()
+
+    if rank != 0:
+        send(np.array([len(part["steps"])], np.int64))
+        for k in keys:
+            send(part[k])
+        return None
+    out = [{k: part[k] for k in keys}]
+    S = part["values"].shape[1]
+    for r in range(1, world):
+        n = int(recv(r, (1,), np.int64)[0])
+        out.append(dict(steps=recv(r, (n,), np.int64), values=recv(r, (n, S, 16), np.float64),
+                        ke_seed=recv(r, (S,), np.float64)))
     return out
 
 
@@ -177,10 +217,17 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
     if verbose and rank == 0:
         print(f"readInpFile:{fname}\nnNode:{glob.nNode}\nnElement:{glob.nElement}\ncontact_flag:{glob.contact_flag}")
         print(f"mass_scaling:{glob.mass_scaling:g}\ntime_num:{time_num:g}\nranks:{world}")
-    if rank == 0 and os.environ.get("HAKAI_HISTORY"):
-        # history output is one-GPU only (hakai_history_enable refuses a rank with a communicator)
-        print("HAKAI_HISTORY is ignored by the N-GPU driver: history output needs the one-GPU driver (hakai.hakai)",
-              file=sys.stderr)
+    # HAKAI_HISTORY=<stride>: the one-GPU driver's history output (hakai_run_inp) -- its sets, its
+    # names and its capacity rule; every rank records the nodes it owns, rank 0 combines at the end
+    hist_stride = int(os.environ.get("HAKAI_HISTORY") or 0)
+    hist_names = None
+    if hist_stride > 0:
+        hist_names, gsets, dropped = glob.history_sets
+        if verbose and rank == 0:
+            for d in dropped:
+                print(f"history: set {d} left out (at most {HISTORY_MAX_SETS} sets)", file=sys.stderr)
+        for sv, (l2g, _) in zip(svs, meta):
+            sv.history_enable(_dist.local_sets(gsets, l2g), stride=hist_stride, capacity=n_steps // hist_stride + 1)
     out = _Output(glob, gdiag, device, out_dir) if rank == 0 else None
 
     def output(idx):
@@ -216,6 +263,13 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
             t0 = t1 + 1
         for sv in svs:
             sv.sync()
+        if hist_stride > 0:  # the ranks' records travel to rank 0 once
+            parts = [sv.history() for sv in svs]
+            if tdist is not None:
+                parts = gather_history(tdist, out_group, rank, world, parts[0], out_dev)
+            if rank == 0:
+                h = history_combine(parts)
+                write_history_csv(os.path.join(out_dir, "history.csv"), hist_names, h["steps"], h["values"], dt)
         if verbose and rank == 0:
             print()
     finally:

@@ -207,7 +207,9 @@ class Solver:
     def history_enable(self, sets=(), stride: int = 1, capacity: int = 1 << 16):
         """Per-step sums over node sets (hakai_history_enable): `sets` is a list of 1-based node id
         arrays (at most 15; set 0, every node, is always there). A record is kept every `stride`
-        states, the newest `capacity` of them."""
+        states, the newest `capacity` of them. On a rank (after set_interface) the ids are the
+        rank's local ones (dist.local_sets), stride and capacity the same on every rank, and the
+        records are the rank's partial sums over the nodes it owns (history_group combines them)."""
         sets = [np.ascontiguousarray(s, np.int64).ravel() for s in sets]
         off = np.zeros(len(sets) + 1, np.int64)
         off[1:] = np.cumsum([len(s) for s in sets])
@@ -230,7 +232,6 @@ class Solver:
         ``values`` (n, sets, 16), ``ke_seed`` (sets,) and one array per field of
         ``_abi.HISTORY_FIELDS`` -- (n, sets, 3) for F_int, F_ext, P, U; (n, sets) for KE, W_int,
         W_ext, W_bc."""
-        from ._abi import HISTORY_FIELDS
         nw, nh = self.history_count()
         if first is None:
             first = nw - nh
@@ -241,10 +242,7 @@ class Solver:
         values = np.zeros((max(n, 0), S, 16))
         ke = np.zeros(S)
         check(self.L.hakai_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values), ptr(ke)))
-        out = dict(steps=steps, values=values, ke_seed=ke)
-        for name, lo, w in HISTORY_FIELDS:
-            out[name] = values[:, :, lo:lo + w] if w > 1 else values[:, :, lo]
-        return out
+        return _history_dict(steps, values, ke)
 
     # -- multi-GPU ---------------------------------------------------------------------------------
     def comm_init(self, rank: int, nranks: int, uid: bytes):
@@ -286,6 +284,37 @@ class Solver:
         hi = np.ascontiguousarray(rank_hi, np.int32)
         check(self.L.hakai_set_interface(self.ctx, len(ln), ptr(ln, I64), ptr(lo, ctypes.c_int32),
                                          ptr(hi, ctypes.c_int32)))
+
+
+def _history_dict(steps, values, ke) -> dict:
+    from ._abi import HISTORY_FIELDS
+    out = dict(steps=steps, values=values, ke_seed=ke)
+    for name, lo, w in HISTORY_FIELDS:
+        out[name] = values[:, :, lo:lo + w] if w > 1 else values[:, :, lo]
+    return out
+
+
+def history_combine(parts: list[dict]) -> dict:
+    """The ranks' partial records (Solver.history() dicts, in rank order) as the record of the whole
+    model (hakai_history_combine): ((p_0 + p_1) + p_2) + ... per value, the same dict as
+    Solver.history()."""
+    shapes = {(p["steps"].shape, p["values"].shape) for p in parts}
+    if len(shapes) != 1:
+        raise ValueError(f"history_combine: the ranks hold different record counts or sets: {sorted(shapes)}")
+    steps = np.ascontiguousarray(np.stack([p["steps"] for p in parts]), np.int64)
+    values = np.ascontiguousarray(np.stack([p["values"] for p in parts]), np.float64)
+    ke = np.ascontiguousarray(np.stack([p["ke_seed"] for p in parts]), np.float64)
+    R, n, S = values.shape[0], values.shape[1], values.shape[2]
+    so, vo, ko = np.zeros(n, np.int64), np.zeros((n, S, 16)), np.zeros(S)
+    check(lib().hakai_history_combine(R, S, n, ptr(steps, I64), ptr(values), ptr(ke), ptr(so, I64), ptr(vo),
+                                      ptr(ko)))
+    return _history_dict(so, vo, ko)
+
+
+def history_group(solvers: list[Solver], first: int | None = None, n: int | None = None) -> dict:
+    """The record of the whole model from a group of ranks (solvers[r] = rank r): every rank's
+    history(first, n), combined in rank order. The same dict as Solver.history()."""
+    return history_combine([sv.history(first, n) for sv in solvers])
 
 
 def step_group(solvers: list[Solver], t_first: float, n_steps: int, d_time: float | None = None):

@@ -23,6 +23,9 @@
 
 namespace hkc {
 int fail(int code, const char* fmt, ...);
+// the drivers' history sets (hakai_history_host.cpp)
+void history_driver_sets(const hakai_inp_model_t* M, std::vector<std::string>& names, std::vector<int64_t>& off,
+                         std::vector<int64_t>& nodes, std::vector<std::string>& dropped);
 }
 using hkc::fail;
 
@@ -808,63 +811,6 @@ int hakai_lumped_mass(int64_t nNode, const double* coordmat, int64_t nElement, c
     return 0;
 }
 
-int hakai_history_write_csv(const char* path, int32_t n_names, const char* const* set_names, int64_t n,
-                            const int64_t* steps, const double* values, double d_time) {
-    static const char* const field[HAKAI_HISTORY_FIELDS] = {"F_int_x", "F_int_y", "F_int_z", "F_ext_x", "F_ext_y", "F_ext_z",
-                                                            "P_x",     "P_y",     "P_z",     "KE",      "W_int",   "W_ext",
-                                                            "W_bc",    "U_x",     "U_y",     "U_z"};
-    if (!path || n_names < 1 || n_names > HAKAI_HISTORY_MAX_SETS + 1 || !set_names || n < 0 ||
-        (n > 0 && (!steps || !values)))
-        return fail(HAKAI_ERR_ARG, "history_write_csv: bad arguments");
-    FILE* fp = std::fopen(path, "w");
-    if (!fp) return fail(HAKAI_ERR_IO, "%s: cannot open for writing", path);
-    std::fprintf(fp, "step,time");
-    for (int s = 0; s < n_names; ++s)
-        for (int f = 0; f < HAKAI_HISTORY_FIELDS; ++f) std::fprintf(fp, ",%s_%s", set_names[s], field[f]);
-    std::fprintf(fp, "\n");
-    const size_t W = (size_t)n_names * HAKAI_HISTORY_FIELDS;
-    for (int64_t i = 0; i < n; ++i) {
-        std::fprintf(fp, "%lld,%.17g", (long long)steps[i], (double)steps[i] * d_time);
-        for (size_t j = 0; j < W; ++j) std::fprintf(fp, ",%.17g", values[(size_t)i * W + j]);
-        std::fprintf(fp, "\n");
-    }
-    const bool bad = std::ferror(fp) != 0;
-    if (std::fclose(fp) != 0 || bad) return fail(HAKAI_ERR_IO, "%s: write failed", path);
-    return 0;
-}
-
-// HAKAI_HISTORY=<stride>: the sets of the driver's history output -- one per instance, then one
-// per *Boundary group (the nodes of its dofs), HAKAI_HISTORY_MAX_SETS in all.
-static void history_sets(const hakai_inp_model_t* M, std::vector<std::string>& names, std::vector<int64_t>& off,
-                         std::vector<int64_t>& nodes, std::vector<std::string>& dropped) {
-    names.assign(1, "all");
-    off.assign(1, 0);
-    auto add = [&](const std::string& name, const std::vector<int64_t>& ns) {
-        if ((int)names.size() > HAKAI_HISTORY_MAX_SETS) {
-            dropped.push_back(name);
-            return;
-        }
-        names.push_back(name);
-        nodes.insert(nodes.end(), ns.begin(), ns.end());
-        off.push_back((int64_t)nodes.size());
-    };
-    for (int i = 0; i < M->n_instance; ++i) {
-        const int64_t n0 = M->instance_node_offset[i];
-        const int64_t n1 = i + 1 < M->n_instance ? M->instance_node_offset[i + 1] : M->nNode;
-        std::vector<int64_t> ns;
-        for (int64_t n = n0; n < n1; ++n) ns.push_back(n + 1);
-        add("inst" + std::to_string(i + 1), ns);
-    }
-    for (int g = 0; g < M->bc.n_groups; ++g) {
-        std::vector<int64_t> ns;
-        for (int64_t en = M->bc.entry_off[g]; en < M->bc.entry_off[g + 1]; ++en)
-            for (int64_t d = M->bc.dof_off[en]; d < M->bc.dof_off[en + 1]; ++d) ns.push_back((M->bc.dofs[d] - 1) / 3 + 1);
-        std::sort(ns.begin(), ns.end());
-        ns.erase(std::unique(ns.begin(), ns.end()), ns.end());
-        add("bc" + std::to_string(g + 1), ns);
-    }
-}
-
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose) {
     hakai_inp_model_t* M = nullptr;
     int r = hakai_inp_read(fname, &M);
@@ -916,7 +862,7 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
     if (hist_stride > 0) {
         std::vector<int64_t> off, nodes;
         std::vector<std::string> dropped;
-        history_sets(M, hist_names, off, nodes, dropped);
+        hkc::history_driver_sets(M, hist_names, off, nodes, dropped);
         if (verbose)
             for (const std::string& d : dropped)
                 std::fprintf(stderr, "history: set %s left out (at most %d sets)\n", d.c_str(), HAKAI_HISTORY_MAX_SETS);

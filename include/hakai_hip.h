@@ -234,10 +234,29 @@ int hakai_set_tuning(hakai_ctx* ctx, const char* key, int64_t value);
  * its d_time. A step a contact overflow poisoned leaves no record and accumulates nothing. The sums
  * are taken in a fixed tree over the node numbers: the same bits for every tuning setting and
  * launch form. hakai_upload_model disables history; hakai_set_bc keeps it.
- * Not supported on a context with a communicator (hakai_comm_init / hakai_comm_init_local):
- * hakai_history_enable returns HAKAI_ERR_STATE there, and both comm calls refuse a context with
- * history enabled. Tuning "history_one_block" (-1 default: by mesh size; 0; 1) picks the reduction's
- * launch form: one workgroup in one launch, or chunk partials and a combining launch. */
+ * Tuning "history_one_block" (-1 default: by mesh size; 0; 1) picks the reduction's launch form:
+ * one workgroup in one launch, or chunk partials and a combining launch.
+ *
+ * On N ranks (a context with a communicator, hakai_comm_init / hakai_comm_init_local) every rank
+ * keeps a PARTIAL record: the same sums, in the same tree over the rank's local node numbers, taken
+ * over the nodes the rank owns. A node shared by ranks r and r+1 is owned by r (the contact search's
+ * owner rule), so a rank owns every local node except those it shares with the rank below; a node
+ * it does not own counts in no set, set 0 included. Each rank has its own ring and its own work
+ * accumulators and nothing is exchanged per step. The record of the whole model is the sum of the
+ * ranks' records in rank order, ((p_0 + p_1) + p_2) + ..., formed on the host by
+ * hakai_history_combine; the same holds for KE_seed, and the works are linear, so the sum of the
+ * ranks' accumulators is the accumulated work and the identity above holds for the combined set 0.
+ * A one-GPU tree's chunks straddle the cuts, so the combined record is NOT the one-GPU record bit for
+ * bit; it is deterministic for a given partition (the same bits for every tuning setting, both
+ * launch forms, an in-process group and RCCL ranks) and within the same rounding bound of the exact
+ * sums. On a rank: hakai_history_enable needs hakai_set_interface first (an empty interface counts;
+ * without it HAKAI_ERR_STATE), set_nodes are the rank's local 1-based ids (both ranks may list a
+ * shared node, only the owner counts it), stride and capacity must be the same on every rank, and
+ * the call is collective like the state calls (every rank, in any order). hakai_comm_init,
+ * hakai_comm_init_local and hakai_set_interface refuse a context with history enabled
+ * (HAKAI_ERR_STATE: disable it first). hakai_history_count / hakai_history_read on a rank return
+ * that rank's partial records. A step that a multi-GPU contact exchange overflow poisoned leaves no
+ * record on any rank; the call runs it again. */
 #define HAKAI_HISTORY_MAX_SETS 15
 #define HAKAI_HISTORY_FIELDS 16
 /* set_off[n_sets+1] into set_nodes (1-based node ids; duplicates within a set are an error; an
@@ -256,6 +275,16 @@ int hakai_history_read(hakai_ctx* ctx, int64_t first, int64_t n, int64_t* steps,
  * time = step * d_time and every value as %.17g (parses back to the same double). */
 int hakai_history_write_csv(const char* path, int32_t n_names, const char* const* set_names, int64_t n,
                             const int64_t* steps, const double* values, double d_time);
+/* Host helper (no GPU): the ranks' partial records into the record of the whole model. Inputs in
+ * rank order, as hakai_history_read returned them for the same [first, first+n) on every rank:
+ * steps[n_ranks][n], values[n_ranks][n][n_total][16], ke_seed[n_ranks][n_total], with n_total =
+ * n_sets + 1. Outputs steps_out[n], values_out[n][n_total][16], ke_seed_out[n_total]: every value is
+ * ((p_0 + p_1) + p_2) + ... over the ranks, one rounding per addition; one rank is the identity.
+ * HAKAI_ERR_ARG: a null array (steps, values and their outputs may be NULL only when n == 0),
+ * n_ranks < 1, n_total outside 1..16, n < 0. HAKAI_ERR_STATE: the ranks' step numbers differ. A
+ * refused call leaves the outputs untouched. */
+int hakai_history_combine(int32_t n_ranks, int32_t n_total, int64_t n, const int64_t* steps, const double* values,
+                          const double* ke_seed, int64_t* steps_out, double* values_out, double* ke_seed_out);
 
 /* ---- contact: all-exterior instance-vs-instance penalty contact --------- */
 /* Enables contact for the uploaded model: contact_flag as readInpFile sets it (1 = *Contact,
@@ -415,6 +444,13 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
  * then "bc<g>" per *Boundary group (the nodes of its dofs), 15 sets at most (verbose: the ones left
  * out are named on stderr); the ring holds the whole run. Without the variable nothing changes. */
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose);
+/* The sets of that history output, for another driver of the same deck (the N-GPU driver, hakai.run):
+ * n_sets (without set 0), set_off[n_sets+1] (room for 16) into set_nodes (global 1-based ids;
+ * NULL: only the offsets, set_off[n_sets] is the room set_nodes needs), names: "all", the n_sets
+ * kept names, then the n_dropped names left out, each ended by a newline (NULL: none).
+ * HAKAI_ERR_ARG if nodes_cap or names_cap is too small. */
+int hakai_inp_history_sets(const hakai_inp_model_t* model, int32_t* n_sets, int64_t* set_off, int64_t* set_nodes,
+                           int64_t nodes_cap, char* names, int64_t names_cap, int32_t* n_dropped);
 
 #ifdef __cplusplus
 }

@@ -217,6 +217,22 @@ function history(c::Ctx, n_total::Integer)
                 c.p, nw - nh, nh, steps, values, ke_seed))
     return steps, values, ke_seed
 end
+# On N ranks (history_enable after set_interface, local node ids) history(c, n_total) returns the
+# rank's partial record over the nodes it owns. history_combine takes the ranks' (steps, values,
+# ke_seed) tuples in rank order and returns the record of the whole model, ((p_0 + p_1) + p_2) + ...
+# per value (hakai_history_combine; host only, no GPU).
+function history_combine(parts::Vector{<:Tuple})
+    R = length(parts); n = length(parts[1][1]); n_total = length(parts[1][3])
+    steps = Int64[]; values = Float64[]; ke_seed = Float64[]
+    for (s, v, k) in parts
+        append!(steps, s); append!(values, vec(v)); append!(ke_seed, k)
+    end
+    so = zeros(Int64, n); vo = zeros(Float64, 16, n_total, n); ko = zeros(Float64, n_total)
+    check(ccall((:hakai_history_combine, lib), Cint,
+                (Int32, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                R, n_total, n, steps, values, ke_seed, so, vo, ko))
+    return so, vo, ko
+end
 
 # cal_node_stress_strain (v2/HAKAI_j.jl:3408-3486) on the device -> the fields of NodeDataType
 # (node_stress / node_strain nNode x 6 like the reference; node_plastic_strain stays zero, :450)

@@ -5,7 +5,7 @@
 
 Each OLD / NEW is a device assembly file (.s), a HIP source (compiled to device assembly with the
 Makefile's flags for that file, no GPU needed) or a source tree (every hakai-fem_amd/csrc/*.hip in
-it). The kernels of each side are collected over all its files and matched by base name (`k_...`;
+it, and csrc/hakai_comm.cpp, whose interface kernels hipcc compiles too). The kernels of each side are collected over all its files and matched by base name (`k_...`;
 a template instantiation keeps its mangled arguments), so a kernel may move between files or
 namespaces. Before comparing, mangled symbols are reduced to the base name, basic-block and other
 local labels are renumbered in order of appearance, and comments, blank lines and assembler
@@ -113,6 +113,7 @@ def side(paths):
     for p in paths:
         if os.path.isdir(p):
             files = sorted(glob.glob(os.path.join(p, "hakai-fem_amd", "csrc", "*.hip")))
+            files += glob.glob(os.path.join(p, "hakai-fem_amd", "csrc", "hakai_comm.cpp"))
         else:
             files = [p]
         for f in files:
