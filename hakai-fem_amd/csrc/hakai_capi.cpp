@@ -20,6 +20,7 @@
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
 #include "hakai_own_plan.hpp"
+#include "hakai_stable_dt.hpp"
 
 using hk::DevMat;
 
@@ -405,6 +406,7 @@ int hakai_destroy(hakai_ctx* c) {
     hkc::graph_free(c);
     dfree(c->d_tstep);
     hkc::history_destroy(c);
+    hkc::stable_dt_destroy(c);
     hkc::comm_destroy(c);
     hkc::free_model(c);
     hkc::free_bc(c);
@@ -440,6 +442,7 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     HIPCHK(hipSetDevice(c->device));
     (void)hipStreamSynchronize(c->stream);
     hkc::history_destroy(c);  // its buffers are sized for the previous mesh: enable again
+    hkc::stable_dt_destroy(c);  // so is the stable-step scratch: the next call allocates it
     hkc::free_model(c);
     // BC tables are sized for the previous mesh (the fused-BC per-dof table has 3nN entries): a new
     // model starts without BCs until hakai_set_bc runs again
@@ -538,6 +541,8 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     c->h_mat.assign(mat.begin(), mat.begin() + nE);
     c->h_young.resize((size_t)nMat);
     for (int i = 0; i < nMat; ++i) c->h_young[i] = mats[i].young;
+    c->h_poisson.resize((size_t)nMat);
+    for (int i = 0; i < nMat; ++i) c->h_poisson[i] = mats[i].poisson;
     c->model_ok = true;
     c->state_ok = false;
     return hakai_reset_state(c, 0, nullptr, nullptr, 1.0);

@@ -12,6 +12,7 @@ namespace hkc {
 struct Comm;     // multi-GPU state (hakai_comm.cpp)
 struct Contact;  // contact search state (hakai_contact_state.hpp)
 struct History;  // history output state (hakai_history.hip)
+struct StableDt; // stable-time-step scratch (hakai_stable_dt.hip)
 int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 }  // namespace hkc
@@ -158,6 +159,10 @@ struct hakai_ctx {
     // history output (hakai_history_enable; hakai_history.hpp has the hooks)
     hkc::History* hist = nullptr;
     int hist_one_block = -1;           // tuning "history_one_block": -1 by size, 0 two launches, 1 one
+    // stable-time-step diagnostic (hakai_stable_dt; hakai_stable_dt.hpp): its scratch, null until the
+    // first call, and the Poisson ratios its material table needs next to h_young
+    hkc::StableDt* sdt = nullptr;
+    std::vector<double> h_poisson;     // per material
 };
 
 

@@ -1,0 +1,357 @@
+// hakai_stable_dt.hip -- the stable-time-step diagnostic (hakai_stable_dt, include/hakai_hip.h): per
+// active element the conventional estimate dt_est = L / c and dt_safe, a guaranteed lower bound of
+// the critical step of the ELASTIC B-bar stiffness against the lumped mass (the plastic tangent is
+// no stiffer; the penalty stiffness of contact is outside it), both at the current configuration,
+// reduced on the device to their minima, the elements that attain them and three counts. Off the
+// hot path, like k_negjac: a kernel of its own, launched only by hakai_stable_dt; it reads coord,
+// the current displacement, the connectivity, the flags and the material ids and writes only its own
+// scratch, so nothing a step reads changes and captured graphs stay valid (no graph_invalidate).
+// The element's arithmetic is hakai_stable_dt_elem.hpp, compiled here without contraction.
+//
+// k_stable_dt: the project's mapping -- 8 lanes per element, lane k = Gauss point k, 32 elements per
+// 256-thread block. Lane k gathers node k's coord and u (the 8 lanes of an element read its 8 nodes
+// in one instruction), the positions go round the 8-lane group by wave shuffles (no LDS, no
+// barrier), every lane forms the 26 terms of its Gauss point and the sums over the Gauss points are
+// the xor-1/2/4 butterfly, the bits of the header's pairwise tree: V and sum s_k on every lane
+// (allreduce8), the 24 gradient sums as a reduce-scatter that leaves node i's three on lane i
+// (sum_scatter8), which takes node i's share of sum g~^2 -- 3 divisions per lane instead of 24.
+// V0 is summed in Gauss-point order from the lanes' determinants, as hakai_lumped_mass does; it is a
+// constant of the model, so a context's first call forms and stores it (k_stable_dt<false>) and the
+// later calls read it (k_stable_dt<true>, a fifth less arithmetic), the same bits.
+// Materials come from a per-call table in global memory: any number of them.
+// Per block: the minimum of each quantity with the lowest element id among equal values, and the
+// counts, combined over the wave with shuffles and ballots and over the four waves through 4 LDS
+// slots; one partial per block. k_stable_dt_finish, one block in a second launch, combines the
+// partials: the launch boundary is the only hand-off between workgroups (no atomics, flags or
+// spins). A minimum with a lowest-id tie rule and integer counts are exact and order-free: the same
+// result for every grid.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "../../include/hakai_hip.h"
+#include "hakai_device.hpp"
+#include "hakai_internal.hpp"
+#include "hakai_stable_dt.hpp"
+#include "hakai_stable_dt_elem.hpp"
+
+using hkc::fail;
+using hkc::hip_fail;
+
+#define HIPCHK(x)                                           \
+    do {                                                    \
+        hipError_t _e = (x);                                \
+        if (_e != hipSuccess) return hip_fail(_e, #x);      \
+    } while (0)
+
+namespace {
+
+constexpr int kEPB = 32;        // elements per block
+constexpr int kThreads = 256;   // 8 lanes per element
+constexpr int kNone = INT_MAX;  // element id of "no active element": loses every tie
+
+// A partial result (a wave's, a block's); element ids local and 0-based.
+struct Part {
+    double est, safe;
+    int e_est, e_safe;
+    int n_active, n_est, n_safe, pad;
+};
+
+// What the finish kernel leaves for the host.
+struct Result {
+    double est, safe;
+    long long e_est, e_safe;
+    long long n_active, n_est, n_safe;
+};
+
+struct Args {
+    const double* coord;
+    const double* u;
+    const int* conn;
+    const int* flag;
+    const int* mat;
+    const hk::StableMat* mats;
+    long long nE;
+    double d_time;       // counts against it (<= 0: none)
+    double* est_elem;    // [nE] or null
+    double* safe_elem;   // [nE] or null
+    Part* part;          // [ceil(nE / 32)]
+    double* v0;          // [nE] the elements' V0: written by the first call, read by the later ones
+};
+
+template <class I>
+__device__ __forceinline__ void take_min(double& v, I& id, double ov, I oid) {
+    if (ov < v || (ov == v && oid < id)) {
+        v = ov;
+        id = oid;
+    }
+}
+
+// The 24 sums S[c][i] = sum_k H_k[c][i] (t[1 + 8c + i] on lane k), left scattered: lane i gets the
+// three of node i. Partners k^1, k^2, k^4 in that order, each lane keeping the nodes whose bit
+// matches its own, so every sum is the pairwise tree ((0+1)+(2+3))+((4+5)+(6+7)) of allreduce8 and
+// of the header's stable_sum8 (an addition commutes), with 21 exchanges instead of 72.
+__device__ __forceinline__ void sum_scatter8(const double (&t)[hk::kStableTerms], double (&out)[3], int k) {
+    const bool b0 = (k & 1) != 0, b1 = (k & 2) != 0, b2 = (k & 4) != 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double w[4], u[2];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {  // nodes 2s + b0
+            const double lo = t[1 + 8 * c + 2 * s], hi = t[1 + 8 * c + 2 * s + 1];
+            w[s] = (b0 ? hi : lo) + hk::dpp<hk::kDppXor1>(b0 ? lo : hi);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s)    // nodes 4s + 2 b1 + b0
+            u[s] = (b1 ? w[2 * s + 1] : w[2 * s]) + hk::dpp<hk::kDppXor2>(b1 ? w[2 * s] : w[2 * s + 1]);
+        out[c] = (b2 ? u[1] : u[0]) + __shfl_xor(b2 ? u[0] : u[1], 4, 8);
+    }
+}
+
+// kHaveV0 false: a context's first call, which also forms every element's V0 (a constant of the
+// model) and stores it; true: the later calls, which read it -- the same bits either way.
+template <bool kHaveV0>
+__global__ __launch_bounds__(kThreads) void k_stable_dt(Args a) {
+    const int tid = threadIdx.x, k = tid & 7;
+    const long long e = (long long)blockIdx.x * kEPB + (tid >> 3);
+    const bool in = e < a.nE;
+    const long long ee = in ? e : a.nE - 1;  // lanes past the end compute the last element and drop it
+    const bool active = in && a.flag[ee] == 1;
+    const long long n = a.conn[8 * ee + k];
+    double Xk[3], xk[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        Xk[c] = a.coord[3 * n + c];
+        xk[c] = a.coord[3 * n + c] + a.u[3 * n + c];
+    }
+    double V0;
+    if constexpr (kHaveV0) {
+        V0 = a.v0[ee];
+    } else {
+        double X[8][3], d0[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) X[i][c] = __shfl(Xk[c], i, 8);
+        const double det0 = hk::stable_det0(k, X);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d0[i] = __shfl(det0, i, 8);
+        V0 = hk::stable_v0(d0);
+        if (in && k == 0) a.v0[e] = V0;
+    }
+    double x[8][3];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[i][c] = __shfl(xk[c], i, 8);
+    double t[hk::kStableTerms];
+    hk::stable_gp(k, x, t);
+    const double V = hk::allreduce8(t[0]), ss = hk::allreduce8(t[25]);
+    double Sn[3];
+    sum_scatter8(t, Sn, k);
+    const double gg = hk::allreduce8(hk::stable_node_gg(Sn[0], Sn[1], Sn[2], V));
+    double est, safe;
+    hk::stable_finish(V, gg, ss, V0, hk::stable_amax(x), a.mats[a.mat[ee]], &est, &safe);
+    if (!active) {
+        est = HUGE_VAL;
+        safe = HUGE_VAL;
+    }
+    if (in && k == 0) {
+        if (a.est_elem) a.est_elem[e] = est;
+        if (a.safe_elem) a.safe_elem[e] = safe;
+    }
+    // the wave's 8 elements: counts from ballots of the elements' first lanes, minima by shuffles
+    // (every lane of an element holds the same pair)
+    const bool lead = active && k == 0, cnt = lead && a.d_time > 0.0;
+    const int n_active = __popcll(__ballot(lead));
+    const int n_est = __popcll(__ballot(cnt && est < a.d_time));
+    const int n_safe = __popcll(__ballot(cnt && safe < a.d_time));
+    int ie = active ? (int)e : kNone, is = ie;
+#pragma unroll
+    for (int m = 8; m < 64; m <<= 1) {
+        const double oe = __shfl_xor(est, m), os = __shfl_xor(safe, m);
+        const int oie = __shfl_xor(ie, m), ois = __shfl_xor(is, m);
+        take_min(est, ie, oe, oie);
+        take_min(safe, is, os, ois);
+    }
+    __shared__ Part w[kThreads / 64];
+    if ((tid & 63) == 0) {
+        Part p;
+        p.est = est;
+        p.safe = safe;
+        p.e_est = ie;
+        p.e_safe = is;
+        p.n_active = n_active;
+        p.n_est = n_est;
+        p.n_safe = n_safe;
+        p.pad = 0;
+        w[tid >> 6] = p;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        Part p = w[0];
+#pragma unroll
+        for (int q = 1; q < kThreads / 64; ++q) {
+            take_min(p.est, p.e_est, w[q].est, w[q].e_est);
+            take_min(p.safe, p.e_safe, w[q].safe, w[q].e_safe);
+            p.n_active += w[q].n_active;
+            p.n_est += w[q].n_est;
+            p.n_safe += w[q].n_safe;
+        }
+        a.part[blockIdx.x] = p;
+    }
+}
+
+// One block: thread t takes the partials t, t + 256, ..., then a tree over the 256 threads in LDS.
+__global__ __launch_bounds__(kThreads) void k_stable_dt_finish(const Part* part, long long nb, Result* out) {
+    __shared__ Result s[kThreads];
+    const int tid = threadIdx.x;
+    Result r;
+    r.est = r.safe = HUGE_VAL;
+    r.e_est = r.e_safe = kNone;
+    r.n_active = r.n_est = r.n_safe = 0;
+    for (long long i = tid; i < nb; i += kThreads) {
+        const Part p = part[i];
+        take_min(r.est, r.e_est, p.est, (long long)p.e_est);
+        take_min(r.safe, r.e_safe, p.safe, (long long)p.e_safe);
+        r.n_active += p.n_active;
+        r.n_est += p.n_est;
+        r.n_safe += p.n_safe;
+    }
+    s[tid] = r;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            Result o = s[tid + h];
+            take_min(s[tid].est, s[tid].e_est, o.est, o.e_est);
+            take_min(s[tid].safe, s[tid].e_safe, o.safe, o.e_safe);
+            s[tid].n_active += o.n_active;
+            s[tid].n_est += o.n_est;
+            s[tid].n_safe += o.n_safe;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) *out = s[0];
+}
+
+template <class T>
+hipError_t dalloc(T** p, size_t n) {
+    *p = nullptr;
+    return hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
+}
+
+template <class T>
+void dfree(T*& p) {
+    if (p) (void)hipFree((void*)p);
+    p = nullptr;
+}
+
+}  // namespace
+
+namespace hkc {
+
+// Scratch of the diagnostic, sized for the context's model at the first call: the block partials,
+// the result, the material table (filled per call: it depends on mass_scaling) and, once a caller
+// asks for them, the per-element arrays.
+struct StableDt {
+    Part* d_part = nullptr;
+    Result* d_res = nullptr;
+    hk::StableMat* d_mats = nullptr;
+    double* d_v0 = nullptr;             // [nE] V0 of every element, valid once a call has completed
+    bool have_v0 = false;
+    double* d_est = nullptr;
+    double* d_safe = nullptr;
+    std::vector<hk::StableMat> h_mats;  // the table of the call in flight (the copy reads it)
+};
+
+void stable_dt_destroy(hakai_ctx* c) {
+    if (!c || !c->sdt) return;
+    (void)hipSetDevice(c->device);
+    dfree(c->sdt->d_part);
+    dfree(c->sdt->d_res);
+    dfree(c->sdt->d_mats);
+    dfree(c->sdt->d_v0);
+    dfree(c->sdt->d_est);
+    dfree(c->sdt->d_safe);
+    delete c->sdt;
+    c->sdt = nullptr;
+}
+
+}  // namespace hkc
+
+extern "C" int hakai_stable_dt(hakai_ctx* c, double mass_scaling, double d_time, hakai_stable_dt_t* out,
+                               double* dt_est_elem, double* dt_safe_elem) {
+    if (!c || !out) return fail(HAKAI_ERR_ARG, "stable_dt: null");
+    if (!(mass_scaling > 0.0) || std::isinf(mass_scaling))
+        return fail(HAKAI_ERR_ARG, "stable_dt: mass_scaling %g (must be positive and finite)", mass_scaling);
+    if (!c->state_ok) return fail(HAKAI_ERR_STATE, "stable_dt without state");
+    HIPCHK(hipSetDevice(c->device));
+    const long long nE = c->nE, nb = (nE + kEPB - 1) / kEPB;
+    hakai_stable_dt_t r;
+    r.dt_est = r.dt_safe = HUGE_VAL;
+    r.element_est = r.element_safe = 0;
+    r.n_active = r.n_est_below = r.n_safe_below = 0;
+    if (nE > 0) {
+        if (!c->sdt) {
+            hkc::StableDt* s = new hkc::StableDt();
+            c->sdt = s;
+            if (dalloc(&s->d_part, (size_t)nb) != hipSuccess || dalloc(&s->d_res, 1) != hipSuccess ||
+                dalloc(&s->d_mats, (size_t)c->nmat) != hipSuccess || dalloc(&s->d_v0, (size_t)nE) != hipSuccess) {
+                hkc::stable_dt_destroy(c);
+                return fail(HAKAI_ERR_DEVICE, "stable_dt: hipMalloc of the scratch failed");
+            }
+        }
+        hkc::StableDt* s = c->sdt;
+        if (dt_est_elem && !s->d_est) HIPCHK(dalloc(&s->d_est, (size_t)nE));
+        if (dt_safe_elem && !s->d_safe) HIPCHK(dalloc(&s->d_safe, (size_t)nE));
+        s->h_mats.resize((size_t)c->nmat);
+        for (int i = 0; i < c->nmat; ++i)
+            s->h_mats[i] = hk::stable_mat(c->h_young[i], c->h_poisson[i], c->h_mats[i].density, mass_scaling);
+        hipStream_t st = c->stream;
+        HIPCHK(hipMemcpyAsync(s->d_mats, s->h_mats.data(), (size_t)c->nmat * sizeof(hk::StableMat),
+                              hipMemcpyHostToDevice, st));
+        Args a;
+        a.coord = c->d_coord;
+        a.u = c->d_u[c->cur];
+        a.conn = c->d_conn;
+        a.flag = c->d_flag;
+        a.mat = c->d_mat;
+        a.mats = s->d_mats;
+        a.nE = nE;
+        a.d_time = d_time;
+        a.est_elem = dt_est_elem ? s->d_est : nullptr;
+        a.safe_elem = dt_safe_elem ? s->d_safe : nullptr;
+        a.part = s->d_part;
+        a.v0 = s->d_v0;
+        if (s->have_v0)
+            hipLaunchKernelGGL(k_stable_dt<true>, dim3((unsigned)nb), dim3(kThreads), 0, st, a);
+        else
+            hipLaunchKernelGGL(k_stable_dt<false>, dim3((unsigned)nb), dim3(kThreads), 0, st, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_stable_dt_finish, dim3(1), dim3(kThreads), 0, st, (const Part*)s->d_part, nb, s->d_res);
+        HIPCHK(hipGetLastError());
+        Result h;
+        HIPCHK(hipMemcpyAsync(&h, s->d_res, sizeof h, hipMemcpyDeviceToHost, st));
+        if (dt_est_elem)
+            HIPCHK(hipMemcpyAsync(dt_est_elem, s->d_est, (size_t)nE * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (dt_safe_elem)
+            HIPCHK(hipMemcpyAsync(dt_safe_elem, s->d_safe, (size_t)nE * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        s->have_v0 = true;
+        r.n_active = h.n_active;
+        r.n_est_below = h.n_est;
+        r.n_safe_below = h.n_safe;
+        if (h.e_est != kNone) {  // (an id is taken with every comparable value, +inf included)
+            r.dt_est = h.est;
+            r.element_est = h.e_est + 1 + c->elem_offset;
+        }
+        if (h.e_safe != kNone) {
+            r.dt_safe = h.safe;
+            r.element_safe = h.e_safe + 1 + c->elem_offset;
+        }
+    }
+    *out = r;
+    return 0;
+}

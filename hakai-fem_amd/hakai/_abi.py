@@ -56,6 +56,12 @@ class StateT(ctypes.Structure):
                 ("integ_triax_stress", PD), ("element_flag", PI64), ("Qe", PD)]
 
 
+class StableDtT(ctypes.Structure):
+    """hakai_stable_dt_t: the two minima, the elements that attain them, the counts against d_time."""
+    _fields_ = [("dt_est", c_double), ("element_est", c_int64), ("dt_safe", c_double), ("element_safe", c_int64),
+                ("n_active", c_int64), ("n_est_below", c_int64), ("n_safe_below", c_int64)]
+
+
 class InpModelT(ctypes.Structure):
     _fields_ = [("nNode", c_int64), ("coordmat", PD), ("nElement", c_int64), ("elementmat", PI64),
                 ("element_material", PI64), ("element_instance", PI64), ("nMat", c_int32),
@@ -138,6 +144,9 @@ def lib() -> ctypes.CDLL:
         "hakai_history_write_csv": (c_int, [c_char_p, c_int32, POINTER(c_char_p), c_int64, PI64, PD, c_double]),
         "hakai_history_combine": (c_int, [c_int32, c_int32, c_int64, PI64, PD, PD, PI64, PD, PD]),
         "hakai_inp_history_sets": (c_int, [POINTER(InpModelT), PI32, PI64, PI64, c_int64, c_char_p, c_int64, PI32]),
+        "hakai_stable_dt": (c_int, [c_void_p, c_double, c_double, POINTER(StableDtT), PD, PD]),
+        "hakai_stable_dt_combine": (c_int, [c_int32, POINTER(StableDtT), POINTER(StableDtT)]),
+        "hakai_stable_dt_write_csv": (c_int, [c_char_p, c_int64, PI64, POINTER(StableDtT), c_double]),
         "hakai_vtk_writer_create": (c_int, [POINTER(c_void_p), c_char_p, c_int64, PD, c_int64, PI64, c_int]),
         "hakai_vtk_writer_submit": (c_int, [c_void_p, c_int, PI64, PD, PD, PD, PD, PD, PD, PD]),
         "hakai_vtk_writer_acquire": (c_int, [c_void_p, c_void_p]),
@@ -167,6 +176,7 @@ def exported_symbols() -> list[str]:
         "hakai_vtk_writer_wait", "hakai_vtk_writer_destroy",
         "hakai_history_enable", "hakai_history_disable", "hakai_history_count", "hakai_history_read",
         "hakai_history_write_csv", "hakai_history_combine", "hakai_inp_history_sets",
+        "hakai_stable_dt", "hakai_stable_dt_combine", "hakai_stable_dt_write_csv",
     ]
 
 

@@ -17,6 +17,11 @@ and capacity rule (hakai_inp_history_sets): every rank records the sums over the
 records travel to rank 0 once at the end of the run, and rank 0 adds them in rank order
 (hakai_history_combine). The VTK files are the same bytes with and without.
 
+Env HAKAI_DT_CHECK=1 also writes out_dir/stable_dt.csv, the one-GPU driver's stable-step records
+(hakai_stable_dt at state 0 and at every output, the deck's mass_scaling and the stepped d_time):
+every rank evaluates its own elements, the records travel to rank 0 once at the end
+(gather_stable_dt), and rank 0 combines them (hakai_stable_dt_combine). Unset, nothing changes.
+
 `local_ranks=N` runs the same partition as an in-process group on one device (tests).
 """
 from __future__ import annotations
@@ -32,7 +37,8 @@ import numpy as np
 from . import dist as _dist
 from ._abi import HISTORY_MAX_SETS, check, lib, ptr
 from .model import read_inp
-from .solver import Solver, State, comm_unique_id, history_combine, step_group, write_history_csv
+from .solver import (STABLE_DT_KEYS, Solver, State, comm_unique_id, history_combine, stable_dt_combine, step_group,
+                     write_history_csv, write_stable_dt_csv)
 
 I64 = ctypes.c_int64
 
@@ -116,6 +122,44 @@ def gather_history(tdist, group, rank: int, world: int, part: dict, device=None)
         n = int(recv(r, (1,), np.int64)[0])
         out.append(dict(steps=recv(r, (n,), np.int64), values=recv(r, (n, S, 16), np.float64),
                         ke_seed=recv(r, (S,), np.float64)))
+    return out
+
+
+def _stable_pack(recs: list) -> np.ndarray:
+    """Solver.stable_dt() dicts as an (n, 7) int64 array, the doubles as their bits."""
+    a = np.zeros((len(recs), len(STABLE_DT_KEYS)), np.int64)
+    for i, r in enumerate(recs):
+        for j, k in enumerate(STABLE_DT_KEYS):
+            a[i, j] = np.float64(r[k]).view(np.int64) if k.startswith("dt_") else int(r[k])
+    return a
+
+
+def _stable_unpack(a: np.ndarray) -> list:
+    return [{k: float(np.int64(row[j]).view(np.float64)) if k.startswith("dt_") else int(row[j])
+             for j, k in enumerate(STABLE_DT_KEYS)} for row in a]
+
+
+def gather_stable_dt(tdist, group, rank: int, world: int, recs: list, device=None):
+    """Rank 0 collects every rank's stable-step records (a list of Solver.stable_dt() dicts, the same
+    number on every rank) once, at the end of the run, as one raw int64 tensor per rank (host
+    tensors over gloo, device tensors over the NCCL group, as gather_history). Returns the lists in
+    rank order on rank 0, None elsewhere."""
+    import torch
+    mine = _stable_pack(recs)
+    if rank != 0:
+        t = torch.from_numpy(mine)
+        tdist.send(t if device is None else t.to(device), 0, group=group)
+        return None
+    out = [recs]
+    for r in range(1, world):
+        if device is None:
+            buf = np.empty(mine.shape, np.int64)
+            tdist.recv(torch.from_numpy(buf), r, group=group)
+        else:
+            t = torch.empty(mine.shape, dtype=torch.int64, device=device)
+            tdist.recv(t, r, group=group)
+            buf = t.cpu().numpy()
+        out.append(_stable_unpack(buf))
     return out
 
 
@@ -229,8 +273,17 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
         for sv, (l2g, _) in zip(svs, meta):
             sv.history_enable(_dist.local_sets(gsets, l2g), stride=hist_stride, capacity=n_steps // hist_stride + 1)
     out = _Output(glob, gdiag, device, out_dir) if rank == 0 else None
+    # HAKAI_DT_CHECK=1: the one-GPU driver's stable-step records (hakai_run_inp) -- at state 0 and at
+    # every output each rank evaluates its own elements (global ids: the element offset is set), the
+    # records travel to rank 0 once at the end, which combines them and writes out_dir/stable_dt.csv
+    dt_check = os.environ.get("HAKAI_DT_CHECK") == "1"
+    dt_steps, dt_recs = [], [[] for _ in svs]
 
     def output(idx):
+        if dt_check:
+            dt_steps.append(idx * d_out)
+            for sv, recs in zip(svs, dt_recs):
+                recs.append(sv.stable_dt(dt, glob.mass_scaling))
         parts = [(mt, _gather_state(sv)) for sv, mt in zip(svs, meta)]
         if tdist is not None:
             parts = gather_parts(tdist, out_group, rank, world, parts[0][1], metas, out_dev)
@@ -270,6 +323,19 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
             if rank == 0:
                 h = history_combine(parts)
                 write_history_csv(os.path.join(out_dir, "history.csv"), hist_names, h["steps"], h["values"], dt)
+        if dt_check:
+            parts = dt_recs
+            if tdist is not None:
+                parts = gather_stable_dt(tdist, out_group, rank, world, dt_recs[0], out_dev)
+            if rank == 0:
+                recs = [stable_dt_combine(list(p)) for p in zip(*parts)]
+                write_stable_dt_csv(os.path.join(out_dir, "stable_dt.csv"), dt_steps, recs, dt)
+                if verbose:
+                    for key, el in (("dt_est", "element_est"), ("dt_safe", "element_safe")):
+                        first = next(((s, r) for s, r in zip(dt_steps, recs) if dt > r[key]), None)
+                        if first:
+                            print(f"stable_dt: step {first[0]}: d_time {dt:.6e} > {key} {first[1][key]:.6e} "
+                                  f"(element {first[1][el]})", file=sys.stderr)
         if verbose and rank == 0:
             print()
     finally:

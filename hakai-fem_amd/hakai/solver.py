@@ -15,7 +15,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._abi import StateT, check, lib, ptr
+from ._abi import StableDtT, StateT, check, lib, ptr
 from .model import Model
 
 I64 = ctypes.c_int64
@@ -244,6 +244,28 @@ class Solver:
         check(self.L.hakai_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values), ptr(ke)))
         return _history_dict(steps, values, ke)
 
+    # -- stable time step -------------------------------------------------------------------------
+    def stable_dt(self, d_time: float | None = None, mass_scaling: float | None = None,
+                  per_element: bool = False) -> dict:
+        """The stable-step diagnostic at the current state (hakai_stable_dt): ``dt_est`` (the
+        conventional L / c, not a bound), ``dt_safe`` (a guaranteed lower bound of the elastic critical
+        step; contact's penalty stiffness is outside it), the 1-based elements that attain them
+        (``element_est``, ``element_safe``; 0: no active element) and ``n_active``, ``n_est_below``,
+        ``n_safe_below`` counted against d_time. Defaults: the model's stepped ``dt`` and its
+        ``mass_scaling``. per_element adds ``dt_est_elem`` and ``dt_safe_elem`` (nElement; +inf where
+        the element is deleted)."""
+        m = self.model
+        r = StableDtT()
+        nE = m.nElement
+        est = np.zeros(nE) if per_element else None
+        safe = np.zeros(nE) if per_element else None
+        check(self.L.hakai_stable_dt(self.ctx, float(m.mass_scaling if mass_scaling is None else mass_scaling),
+                                     float(m.dt if d_time is None else d_time), ctypes.byref(r), ptr(est), ptr(safe)))
+        out = _stable_dict(r)
+        if per_element:
+            out.update(dt_est_elem=est, dt_safe_elem=safe)
+        return out
+
     # -- multi-GPU ---------------------------------------------------------------------------------
     def comm_init(self, rank: int, nranks: int, uid: bytes):
         buf = (ctypes.c_uint8 * 128).from_buffer_copy(uid)
@@ -317,6 +339,60 @@ def history_group(solvers: list[Solver], first: int | None = None, n: int | None
     return history_combine([sv.history(first, n) for sv in solvers])
 
 
+STABLE_DT_KEYS = tuple(name for name, _ in StableDtT._fields_)
+
+
+def _stable_dict(r: StableDtT) -> dict:
+    return {k: getattr(r, k) for k in STABLE_DT_KEYS}
+
+
+def _stable_struct(d: dict, r: StableDtT | None = None) -> StableDtT:
+    r = StableDtT() if r is None else r
+    for (k, t) in StableDtT._fields_:
+        setattr(r, k, float(d[k]) if t is ctypes.c_double else int(d[k]))
+    return r
+
+
+def stable_dt_combine(parts: list[dict]) -> dict:
+    """The ranks' Solver.stable_dt() dicts as the whole model's (hakai_stable_dt_combine): the minimum
+    over the ranks, an equal value to the lowest element id, counts summed."""
+    arr = (StableDtT * len(parts))()
+    for i, p in enumerate(parts):
+        _stable_struct(p, arr[i])
+    out = StableDtT()
+    check(lib().hakai_stable_dt_combine(len(parts), arr, ctypes.byref(out)))
+    return _stable_dict(out)
+
+
+def stable_dt_group(solvers: list[Solver], d_time: float | None = None, mass_scaling: float | None = None) -> dict:
+    """The diagnostic of the whole model from a group of ranks (element offsets set): every rank's
+    stable_dt on its own elements, combined. Element ids are global."""
+    return stable_dt_combine([sv.stable_dt(d_time, mass_scaling) for sv in solvers])
+
+
+def write_stable_dt_csv(path: str, steps, records: list[dict], d_time: float):
+    """Stable-step records (Solver.stable_dt() dicts, one per entry of steps) as CSV
+    (hakai_stable_dt_write_csv)."""
+    steps = np.ascontiguousarray(steps, np.int64)
+    assert len(steps) == len(records), (len(steps), len(records))
+    arr = (StableDtT * max(len(records), 1))()
+    for i, p in enumerate(records):
+        _stable_struct(p, arr[i])
+    check(lib().hakai_stable_dt_write_csv(str(path).encode(), len(records), ptr(steps, I64), arr, float(d_time)))
+
+
+def read_stable_dt_csv(path: str) -> dict:
+    """A stable_dt.csv back as dict(steps, time, d_time, records): the same doubles."""
+    with open(path) as fh:
+        head = fh.readline().strip().split(",")
+        rows = [ln.strip().split(",") for ln in fh if ln.strip()]
+    assert head == ["step", "time", "d_time", *STABLE_DT_KEYS], head
+    conv = [float if t is ctypes.c_double else int for _, t in StableDtT._fields_]
+    return dict(steps=np.array([int(r[0]) for r in rows], np.int64), time=np.array([float(r[1]) for r in rows]),
+                d_time=np.array([float(r[2]) for r in rows]),
+                records=[{k: f(x) for k, f, x in zip(STABLE_DT_KEYS, conv, r[3:])} for r in rows])
+
+
 def step_group(solvers: list[Solver], t_first: float, n_steps: int, d_time: float | None = None):
     """Advance an in-process group (hakai_comm_init_local, solvers[r] = rank r) in lockstep
     (hakai_step_group): per step every rank's contact search, then every rank's exchange and update."""
@@ -385,5 +461,6 @@ def read_history_csv(path: str) -> dict:
 
 def hakai(fname: str, out_dir: str = "temp", device: int = 0, verbose: bool = True):
     """HAKAI(fname) (v2/HAKAI_j.jl:81): run the deck on the GPU and write out_dir/file%03d.vtk.
-    Env HAKAI_HISTORY=<stride> also writes out_dir/history.csv (hakai_run_inp)."""
+    Env HAKAI_HISTORY=<stride> also writes out_dir/history.csv, env HAKAI_DT_CHECK=1 also
+    out_dir/stable_dt.csv (hakai_run_inp)."""
     check(lib().hakai_run_inp(str(fname).encode(), str(out_dir).encode(), device, int(verbose)))

@@ -896,6 +896,32 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
         if ((q = hakai_vtk_writer_commit(w, idx))) return q;
         return sync_out ? hakai_vtk_writer_wait(w) : 0;
     };
+    // HAKAI_DT_CHECK=1: hakai_stable_dt at state 0 and at every output, with the deck's mass_scaling
+    // and the stepped d_time; written to out_dir/stable_dt.csv at the end
+    const char* dv = std::getenv("HAKAI_DT_CHECK");
+    const bool dt_check = dv && dv[0] == '1' && dv[1] == '\0';
+    std::vector<int64_t> dt_steps;
+    std::vector<hakai_stable_dt_t> dt_recs;
+    bool warned_est = false, warned_safe = false;
+    auto check_dt = [&](long long step) -> int {
+        hakai_stable_dt_t s;
+        int q = hakai_stable_dt(c, M->mass_scaling, d_time, &s, nullptr, nullptr);
+        if (q) return q;
+        dt_steps.push_back(step);
+        dt_recs.push_back(s);
+        if (verbose && !warned_est && d_time > s.dt_est) {
+            warned_est = true;
+            std::fprintf(stderr, "stable_dt: step %lld: d_time %.6e > dt_est %.6e (element %lld)\n", step, d_time,
+                         s.dt_est, (long long)s.element_est);
+        }
+        if (verbose && !warned_safe && d_time > s.dt_safe) {
+            warned_safe = true;
+            std::fprintf(stderr, "stable_dt: step %lld: d_time %.6e > dt_safe %.6e (element %lld)\n", step, d_time,
+                         s.dt_safe, (long long)s.element_safe);
+        }
+        return 0;
+    };
+    if (dt_check && (r = check_dt(0))) return r;
     if ((r = output(0))) return r;
     int i_out = 1;
     long long t0 = 1, reported = 0;
@@ -913,6 +939,7 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
             std::fflush(stdout);
         }
         if (d_out > 0 && t1 % d_out == 0) {
+            if (dt_check && (r = check_dt(t1))) return r;
             if ((r = output(i_out))) return r;
             ++i_out;
         }
@@ -932,6 +959,12 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
         const std::string path = std::string(out_dir) + "/history.csv";
         if ((r = hakai_history_write_csv(path.c_str(), (int32_t)names.size(), names.data(), nh, steps.data(),
                                          values.data(), d_time)))
+            return r;
+    }
+    if (dt_check) {
+        const std::string path = std::string(out_dir) + "/stable_dt.csv";
+        if ((r = hakai_stable_dt_write_csv(path.c_str(), (int64_t)dt_steps.size(), dt_steps.data(), dt_recs.data(),
+                                           d_time)))
             return r;
     }
     if (verbose) std::printf("\n");

@@ -286,6 +286,50 @@ int hakai_history_write_csv(const char* path, int32_t n_names, const char* const
 int hakai_history_combine(int32_t n_ranks, int32_t n_total, int64_t n, const int64_t* steps, const double* values,
                           const double* ke_seed, int64_t* steps_out, double* values_out, double* ke_seed_out);
 
+/* ---- stable time step: per-element estimate and lower bound, reduced on the device ----------- */
+/* The reference takes its step from the deck (v2/HAKAI_j.jl:112-116) and never checks it against the
+ * mesh. hakai_stable_dt evaluates, for every active element (element_flag == 1) at the CURRENT
+ * configuration x = coord + disp, two numbers and reduces them on the device (a separate kernel; it
+ * needs a state, runs on the context's stream, synchronises, and writes nothing a step reads: the
+ * steps before and after it, captured graphs included, are the same bits with and without it).
+ * With P_k the cal_Pusai_hexa table at Gauss point k, J_k = P_k x^T, a_k = |det J_k|,
+ * G_k = J_k^-1 P_k, V = sum_k a_k, V0 = sum_k det(P_k coord^T) (the volume hakai_lumped_mass forms),
+ * rho' = density * mass_scaling, M = E (1 - nu) / ((1 + nu)(1 - 2 nu)), Kb = E / (3 (1 - 2 nu)),
+ * mu = E / (2 (1 + nu)):
+ *   dt_est   the conventional estimate L / c: L = V / A_max (A_max the largest of the six face areas,
+ *            each 1/2 |d1 x d2| of the face's diagonals), c = sqrt(M / rho'). What other codes
+ *            print; NOT a bound in either direction (dense eigensolves: 0.36 .. 1.73 of the true
+ *            critical step, 1.06 .. 1.20 on cube meshes at nu >= 0.3).
+ *   dt_safe  2 sqrt(m_e / kappa), m_e = rho' V0 / 8, kappa = Kb V sum g~^2 + 2 mu sum_k a_k sum G_k^2
+ *            with g~ = (sum_k a_k G_k) / V the B-bar mean gradient: kappa bounds the largest
+ *            eigenvalue of the element's ELASTIC B-bar stiffness, so the minimum over the elements is
+ *            a guaranteed lower bound of the linear critical step 2 / omega_max when diag_M is the
+ *            lumped mass times mass_scaling (what every driver uploads). The plastic tangent is no
+ *            stiffer; the PENALTY STIFFNESS OF CONTACT IS NOT COVERED. (DESIGN.md section 2,
+ *            "Stable time step", has the derivation.)
+ * An active element with V0 <= 0, V == 0 or A_max == 0 reports 0 for both; a deleted element reports
+ * +inf and counts nowhere. The sums over the Gauss points are one fixed pairwise tree and the
+ * minimum and the counts are exact, so the result is the same bits for every grid and on the host
+ * (csrc/hakai_stable_dt_elem.hpp is the one definition). */
+typedef struct {
+    double dt_est;   int64_t element_est;    /* 1-based + the context's element offset; 0: no active element (dt = +inf) */
+    double dt_safe;  int64_t element_safe;   /* equal values: the lowest element id */
+    int64_t n_active, n_est_below, n_safe_below;   /* elements with dt < d_time; 0 when d_time <= 0 */
+} hakai_stable_dt_t;
+/* mass_scaling > 0 (the factor diag_M was built with), d_time the step to count against (<= 0: no
+ * counts). dt_est_elem / dt_safe_elem: nElement values each in element order, or NULL. */
+int hakai_stable_dt(hakai_ctx* ctx, double mass_scaling, double d_time, hakai_stable_dt_t* out,
+                    double* dt_est_elem, double* dt_safe_elem);
+/* Host helper (no GPU): the ranks' results into the whole model's -- the minimum over the ranks, an
+ * equal value goes to the lowest element id (a rank without an active element, element 0, never
+ * wins), the counts are summed. HAKAI_ERR_ARG: n_ranks < 1 or a null pointer. */
+int hakai_stable_dt_combine(int32_t n_ranks, const hakai_stable_dt_t* parts, hakai_stable_dt_t* out);
+/* Host helper (no GPU): n records as CSV, header
+ * step,time,d_time,dt_est,element_est,dt_safe,element_safe,n_active,n_est_below,n_safe_below,
+ * time = steps[i] * d_time, every double as %.17g (parses back to the same double; inf as "inf"). */
+int hakai_stable_dt_write_csv(const char* path, int64_t n, const int64_t* steps, const hakai_stable_dt_t* rec,
+                              double d_time);
+
 /* ---- contact: all-exterior instance-vs-instance penalty contact --------- */
 /* Enables contact for the uploaded model: contact_flag as readInpFile sets it (1 = *Contact,
  * 2 = HAKAIoption=self-contact; v2/readInpFile_j.jl:1046-1060), element_instance = instance
@@ -442,7 +486,12 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
  * Env HAKAI_HISTORY=<stride> (>= 1) enables history output for the run and writes
  * out_dir/history.csv (hakai_history_write_csv) at the end: set "all", then "inst<i>" per instance,
  * then "bc<g>" per *Boundary group (the nodes of its dofs), 15 sets at most (verbose: the ones left
- * out are named on stderr); the ring holds the whole run. Without the variable nothing changes. */
+ * out are named on stderr); the ring holds the whole run. Without the variable nothing changes.
+ * Env HAKAI_DT_CHECK=1 records hakai_stable_dt at state 0 and at every VTK output (the deck's
+ * mass_scaling, the stepped d_time = increment * sqrt(mass_scaling)) and writes
+ * out_dir/stable_dt.csv (hakai_stable_dt_write_csv) at the end; verbose: one stderr line the first
+ * time d_time > dt_est and one the first time d_time > dt_safe, each naming the element. The VTK
+ * files and stdout are the same bytes with and without; unset, nothing changes. */
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose);
 /* The sets of that history output, for another driver of the same deck (the N-GPU driver, hakai.run):
  * n_sets (without set 0), set_off[n_sets+1] (room for 16) into set_nodes (global 1-based ids;
