@@ -135,7 +135,9 @@ int hakai_deleted(hakai_ctx* ctx, int64_t* n_deleted, int64_t* log, int64_t cap)
 int hakai_negative_jacobians(hakai_ctx* ctx, int64_t* n);
 
 /* GP -> node averages for output, on device (cal_node_stress_strain, v2/HAKAI_j.jl:3408-3486).
- * node_stress/node_strain are nN x 6 row-major; any pointer may be NULL. */
+ * node_stress/node_strain are nN x 6 row-major; any pointer may be NULL. The divisor is the node's
+ * number of incidences; the reference's (:3458) counts an element that lists a node twice once, so
+ * the two differ only for such an element, which none of the committed decks has. */
 int hakai_node_stress_strain(hakai_ctx* ctx, double* node_stress, double* node_strain,
                              double* node_eq_plastic_strain, double* node_mises_stress,
                              double* node_triax_stress);
