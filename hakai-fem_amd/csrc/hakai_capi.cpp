@@ -19,6 +19,7 @@
 #include "hakai_history.hpp"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
+#include "hakai_loads.hpp"
 #include "hakai_own_plan.hpp"
 #include "hakai_stable_dt.hpp"
 
@@ -87,6 +88,7 @@ static void own_free(hakai_ctx* c) {
 
 static void free_model(hakai_ctx* c) {
     contact_destroy(c);
+    loads_destroy(c);  // sized and validated for the previous mesh
     dfree(c->d_coord);
     dfree(c->d_u[0]);
     dfree(c->d_u[1]);
@@ -999,6 +1001,10 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
             if (rc) return rc;
         }
         na.fext = c->d_fext;
+    }
+    if (c->loads) {  // external loads: contact force + loads -> the step's total external force
+        if ((rc = hkc::loads_step(c, t, d_time, na.fext))) return rc;
+        na.fext = c->d_ftot;  // = hkc::step_fext(c), what the interface fix takes too
     }
     rc = hkc::comm_pre_nodal(c);
     if (rc) return rc;

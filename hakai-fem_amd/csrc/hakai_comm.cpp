@@ -484,13 +484,13 @@ int comm_post_nodal(hakai_ctx* c, double d_time, CommFix* fix) {
         hipLaunchKernelGGL(k_fix_own, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn,
                            m->n_dn, c->d_own_rp, c->d_own_ridx, c->d_own_rows, m->nslot, m->d_up_sendP[par],
                            m->d_up_recvC, m->d_dn_recvP, m->d_saved, c->d_u[c->cur], c->d_u[1 - c->cur], c->d_mass,
-                           c->contact ? c->d_fext : nullptr, d_time, c->d_poison);
+                           step_fext(c), d_time, c->d_poison);
         HIPCHK(hipGetLastError());
     } else if (!c->q_from_buf) {  // an uploaded Q already holds the global sum
         const int n = m->n_up + m->n_dn;
         hipLaunchKernelGGL(k_fix, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn, m->n_dn,
                            c->d_inc_ptr, c->d_inc, c->d_fe, m->nslot, m->d_up_sendP[par], m->d_up_recvC, m->d_dn_recvP,
-                           m->d_saved, c->d_u[c->cur], c->d_u[1 - c->cur], c->d_mass, c->contact ? c->d_fext : nullptr,
+                           m->d_saved, c->d_u[c->cur], c->d_u[1 - c->cur], c->d_mass, step_fext(c),
                            d_time, c->d_poison);
         HIPCHK(hipGetLastError());
     }

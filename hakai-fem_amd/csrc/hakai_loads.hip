@@ -1,0 +1,311 @@
+// hakai_loads.hip -- external loads (hakai_set_loads, include/hakai_hip.h): concentrated nodal
+// forces, gravity and follower face pressure, summed with the step's contact force into the total
+// external force d_ftot that the nodal update, the interface fix and the history output consume.
+//
+// k_loads: ONE launch per step, one thread per node in 256-thread blocks over all nodes, no atomics.
+// A node's sum has a fixed order (the header states it), so a thread GATHERS: its concentrated
+// entries from a per-node list, the gravity entries, and its pressure contributions from a CSR node
+// -> (entry, corner) that the host planner (hakai_loads_plan.cpp) built in ascending entry order. For
+// a pressure contribution the thread loads the four corners of the face at the current configuration
+// coord + u and evaluates only its own corner's F_a through hakai_loads_face.hpp -- g1, g2 and h are
+// formed about four times per face over the launch, the price of a deterministic sum in one launch
+// (small decks are launch-bound: a second launch would cost more than the arithmetic).
+// The node's own operands (contact force, mass, list bounds) are loaded before the dependent gathers,
+// as k_nodal does; which kinds of load exist is a launch-time constant (template parameters), so a
+// node of a gravity-only model runs no list code and no runtime branch joins the loads; the time, the
+// gravity entries and their amplitude tables are uniform over the launch.
+// Compiled without contraction: the operation order of the header is the definition
+// (tests/loads_ref.py restates it, tests/test_gpu_loads.py compares bit for bit).
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/hakai_hip.h"
+#include "hakai_history.hpp"
+#include "hakai_internal.hpp"
+#include "hakai_loads.hpp"
+#include "hakai_loads_face.hpp"
+#include "hakai_loads_plan.hpp"
+
+using hkc::fail;
+using hkc::hip_fail;
+
+#define HIPCHK(x)                                           \
+    do {                                                    \
+        hipError_t _e = (x);                                \
+        if (_e != hipSuccess) return hip_fail(_e, #x);      \
+    } while (0)
+
+namespace {
+
+constexpr int kThreads = 256;
+
+struct LoadArgs {
+    const double* fc;      // the step's contact force [3nN], or null (+0.0)
+    const double* mass;    // [nN]
+    const double* coord;   // [3nN]
+    const double* u;       // [3nN] the displacement the nodal update reads
+    const int* conn;       // [8nE]
+    const int* flag;       // [nE]
+    double* ftot;          // [3nN]
+    long long nN;
+    double ct;             // t * d_time
+    const double* t_rd;    // graph mode: ct = (*t_rd + 1.0) * dt, read on the device
+    double dt;
+    const int* amp_n;
+    const int* amp_off;
+    const double* amp_t;
+    const double* amp_v;
+    const int* cl_ptr;
+    const int* cl_comp;
+    const int* cl_amp;
+    const double* cl_val;
+    int n_grav;
+    const double* g_acc;
+    const int* g_amp;
+    const int* pr_ptr;
+    const int* pr_ent;
+    const int* pr_elem;
+    const int* pr_code;
+    const int* pr_amp;
+    const double* pr_val;
+};
+
+__device__ __forceinline__ double amp_of(const LoadArgs& a, int table, double ct) {
+    if (table < 0) return 1.0;
+    const int off = a.amp_off[table];
+    return hk::loads_amp(a.amp_n[table], a.amp_t + off, a.amp_v + off, ct);
+}
+
+// FC: a contact force is added to; CL / GR / PR: concentrated, gravity, pressure entries exist.
+template <bool FC, bool CL, bool GR, bool PR>
+__global__ __launch_bounds__(kThreads) void k_loads(LoadArgs a) {
+#pragma clang fp contract(off)
+    const long long n = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (n >= a.nN) return;
+    // the node's own operands, in flight together
+    double f0 = FC ? a.fc[3 * n + 0] : 0.0;
+    double f1 = FC ? a.fc[3 * n + 1] : 0.0;
+    double f2 = FC ? a.fc[3 * n + 2] : 0.0;
+    const double m = GR ? a.mass[n] : 0.0;
+    const int c0 = CL ? a.cl_ptr[n] : 0, c1 = CL ? a.cl_ptr[n + 1] : 0;
+    const int p0 = PR ? a.pr_ptr[n] : 0, p1 = PR ? a.pr_ptr[n + 1] : 0;
+    const double ct = a.t_rd ? (*a.t_rd + 1.0) * a.dt : a.ct;  // t * d_time, as on the host
+    if (CL) {
+        for (int j = c0; j < c1; ++j) {
+            const double v = a.cl_val[j] * amp_of(a, a.cl_amp[j], ct);
+            const int cc = a.cl_comp[j];
+            f0 = cc == 0 ? f0 + v : f0;
+            f1 = cc == 1 ? f1 + v : f1;
+            f2 = cc == 2 ? f2 + v : f2;
+        }
+    }
+    if (GR) {
+        for (int g = 0; g < a.n_grav; ++g) {  // uniform: scalar loads
+            const double amp = amp_of(a, a.g_amp[g], ct);
+            f0 = f0 + m * (a.g_acc[3 * g + 0] * amp);
+            f1 = f1 + m * (a.g_acc[3 * g + 1] * amp);
+            f2 = f2 + m * (a.g_acc[3 * g + 2] * amp);
+        }
+    }
+    if (PR) {
+        for (int j = p0; j < p1; ++j) {
+            const int ent = a.pr_ent[j];
+            const int k = ent >> 2, corner = ent & 3;
+            const long long e = a.pr_elem[k];
+            const unsigned code = (unsigned)a.pr_code[k];
+            const int active = a.flag[e];
+            const double pa = a.pr_val[k] * amp_of(a, a.pr_amp[k], ct);
+            double x[4][3];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const long long nq = a.conn[8 * e + hk::loads_code_node(code, q)];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) x[q][c] = a.coord[3 * nq + c] + a.u[3 * nq + c];
+            }
+            double F[3];
+            hk::loads_face_corner(x, corner, pa, F);
+            if (active == 1) {  // a deleted element's face stops loading
+                f0 = f0 + F[0];
+                f1 = f1 + F[1];
+                f2 = f2 + F[2];
+            }
+        }
+    }
+    a.ftot[3 * n + 0] = f0;
+    a.ftot[3 * n + 1] = f1;
+    a.ftot[3 * n + 2] = f2;
+}
+
+template <bool FC, bool CL, bool GR>
+void launch_pr(const LoadArgs& a, bool pr, unsigned grid, hipStream_t s) {
+    if (pr)
+        hipLaunchKernelGGL((k_loads<FC, CL, GR, true>), dim3(grid), dim3(kThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_loads<FC, CL, GR, false>), dim3(grid), dim3(kThreads), 0, s, a);
+}
+template <bool FC, bool CL>
+void launch_gr(const LoadArgs& a, bool gr, bool pr, unsigned grid, hipStream_t s) {
+    if (gr)
+        launch_pr<FC, CL, true>(a, pr, grid, s);
+    else
+        launch_pr<FC, CL, false>(a, pr, grid, s);
+}
+template <bool FC>
+void launch_cl(const LoadArgs& a, bool cl, bool gr, bool pr, unsigned grid, hipStream_t s) {
+    if (cl)
+        launch_gr<FC, true>(a, gr, pr, grid, s);
+    else
+        launch_gr<FC, false>(a, gr, pr, grid, s);
+}
+
+template <class T>
+hipError_t upload(std::vector<void*>& owned, const T** d, const std::vector<T>& h, hipStream_t s) {
+    *d = nullptr;
+    if (h.empty()) return hipSuccess;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, h.size() * sizeof(T));
+    if (e != hipSuccess) return e;
+    owned.push_back(p);
+    *d = (const T*)p;
+    return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
+}
+
+}  // namespace
+
+namespace hkc {
+
+// Device copy of a plan (hakai_loads_plan.hpp) and the total external force of the step.
+struct Loads {
+    std::vector<void*> owned;  // every device allocation below
+    LoadArgs a;                // the plan's pointers; the per-step fields are filled at launch
+    bool cl = false, gr = false, pr = false;
+};
+
+static void loads_free(Loads* L) {
+    if (!L) return;
+    for (void* p : L->owned) (void)hipFree(p);
+    delete L;
+}
+
+void loads_destroy(hakai_ctx* c) {
+    if (!c || !c->loads) return;
+    (void)hipSetDevice(c->device);
+    loads_free(c->loads);
+    c->loads = nullptr;
+    c->d_ftot = nullptr;  // (owned by the list above)
+}
+
+static int loads_launch(hakai_ctx* c, double t, double d_time, const double* fc, const double* t_rd, hipStream_t s) {
+    Loads* L = c->loads;
+    LoadArgs a = L->a;
+    a.fc = fc;
+    a.mass = c->d_mass;
+    a.coord = c->d_coord;
+    a.u = c->d_u[c->cur];
+    a.conn = c->d_conn;
+    a.flag = c->d_flag;
+    a.ftot = c->d_ftot;
+    a.nN = c->nN;
+    a.ct = t * d_time;
+    a.t_rd = t_rd;
+    a.dt = d_time;
+    const unsigned grid = (unsigned)((c->nN + kThreads - 1) / kThreads);
+    if (fc)
+        launch_cl<true>(a, L->cl, L->gr, L->pr, grid, s);
+    else
+        launch_cl<false>(a, L->cl, L->gr, L->pr, grid, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int loads_step(hakai_ctx* c, double t, double d_time, const double* fc) {
+    if (!c->loads) return 0;
+    return loads_launch(c, t, d_time, fc, c->g_trd, c->stream);
+}
+
+}  // namespace hkc
+
+extern "C" {
+
+int hakai_clear_loads(hakai_ctx* c) {
+    if (c) hkc::graph_invalidate(c);  // the launch sequence changes
+    if (!c) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->model_ok) return fail(HAKAI_ERR_STATE, "clear_loads before upload_model");
+    if (!c->loads) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    hkc::loads_destroy(c);
+    return hkc::history_restart(c);  // W_ext changes its meaning
+}
+
+int hakai_set_loads(hakai_ctx* c, const hakai_loads_t* in) {
+    if (c) hkc::graph_invalidate(c);  // the launch sequence changes
+    if (!c || !in) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->model_ok) return fail(HAKAI_ERR_STATE, "set_loads before upload_model");
+    hk::LoadsPlan P;
+    std::string err;
+    if (hk::loads_plan(*in, c->nN, c->nE, c->h_conn.data(), P, err)) return fail(HAKAI_ERR_ARG, "%s", err.c_str());
+    if (c->comm && in->n_press > 0)
+        return fail(HAKAI_ERR_STATE, "set_loads: face pressure on a context with a communicator is not supported "
+                    "(a face across a cut needs nodes the rank does not hold)");
+    if (in->n_cload == 0 && in->n_grav == 0 && in->n_press == 0) return hakai_clear_loads(c);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    hkc::Loads* L = new hkc::Loads();
+    std::memset(&L->a, 0, sizeof L->a);
+    LoadArgs& a = L->a;
+    void* ftot = nullptr;
+    hipError_t e = hipMalloc(&ftot, 3 * (size_t)c->nN * sizeof(double));
+    if (e == hipSuccess) L->owned.push_back(ftot);
+    if (e == hipSuccess) e = upload(L->owned, &a.amp_n, P.amp_n, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.amp_off, P.amp_off, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.amp_t, P.amp_t, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.amp_v, P.amp_v, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.cl_ptr, P.cl_ptr, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.cl_comp, P.cl_comp, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.cl_amp, P.cl_amp, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.cl_val, P.cl_val, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.g_acc, P.g_acc, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.g_amp, P.g_amp, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.pr_ptr, P.pr_ptr, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.pr_ent, P.pr_ent, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.pr_elem, P.pr_elem, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.pr_code, P.pr_code, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.pr_amp, P.pr_amp, s);
+    if (e == hipSuccess) e = upload(L->owned, &a.pr_val, P.pr_val, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the plan's vectors go out of scope
+    if (e != hipSuccess) {
+        hkc::loads_free(L);
+        return hip_fail(e, "set_loads: device copy of the plan");
+    }
+    a.n_grav = (int)P.g_amp.size();
+    L->cl = !P.cl_ptr.empty();
+    L->gr = a.n_grav > 0;
+    L->pr = !P.pr_ptr.empty();
+    hkc::loads_destroy(c);
+    c->loads = L;
+    c->d_ftot = (double*)ftot;
+    return hkc::history_restart(c);  // W_ext changes its meaning
+}
+
+int hakai_load_force(hakai_ctx* c, double t, double d_time, double* f) {
+    if (!c || !f) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->state_ok) return fail(HAKAI_ERR_STATE, "load_force without state");
+    const size_t fn = 3 * (size_t)c->nN;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->loads) {
+        for (size_t i = 0; i < fn; ++i) f[i] = 0.0;
+        return 0;
+    }
+    // d_ftot is rewritten whole by every step before anything reads it: the probe may use it
+    if (int r = hkc::loads_launch(c, t, d_time, nullptr, nullptr, c->stream)) return r;
+    HIPCHK(hipMemcpyAsync(f, c->d_ftot, fn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -62,6 +62,15 @@ class StableDtT(ctypes.Structure):
                 ("n_active", c_int64), ("n_est_below", c_int64), ("n_safe_below", c_int64)]
 
 
+class LoadsT(ctypes.Structure):
+    """hakai_loads_t: amplitude tables, concentrated loads, gravity, face pressure."""
+    _fields_ = [("n_amp", c_int32), ("amp_n", PI32), ("amp_off", PI64), ("amp_time", PD), ("amp_value", PD),
+                ("n_cload", c_int64), ("cload_dof", PI64), ("cload_value", PD), ("cload_amp", PI32),
+                ("n_grav", c_int32), ("grav_accel", PD), ("grav_amp", PI32),
+                ("n_press", c_int64), ("press_elem", PI64), ("press_face", PI32), ("press_value", PD),
+                ("press_amp", PI32)]
+
+
 class InpModelT(ctypes.Structure):
     _fields_ = [("nNode", c_int64), ("coordmat", PD), ("nElement", c_int64), ("elementmat", PI64),
                 ("element_material", PI64), ("element_instance", PI64), ("nMat", c_int32),
@@ -70,7 +79,7 @@ class InpModelT(ctypes.Structure):
                 ("n_ic_dofs", c_int64), ("ic_dofs", PI64), ("ic_values", PD), ("n_instance", c_int32),
                 ("instance_node_offset", PI64), ("instance_element_offset", PI64),
                 ("instance_nElement", PI64), ("n_cp", c_int32), ("cp_instance", PI32), ("cp_elem_off", PI64),
-                ("cp_elems", PI64)]
+                ("cp_elems", PI64), ("loads", LoadsT)]
 
 
 class HakaiError(RuntimeError):
@@ -147,6 +156,9 @@ def lib() -> ctypes.CDLL:
         "hakai_stable_dt": (c_int, [c_void_p, c_double, c_double, POINTER(StableDtT), PD, PD]),
         "hakai_stable_dt_combine": (c_int, [c_int32, POINTER(StableDtT), POINTER(StableDtT)]),
         "hakai_stable_dt_write_csv": (c_int, [c_char_p, c_int64, PI64, POINTER(StableDtT), c_double]),
+        "hakai_set_loads": (c_int, [c_void_p, POINTER(LoadsT)]),
+        "hakai_clear_loads": (c_int, [c_void_p]),
+        "hakai_load_force": (c_int, [c_void_p, c_double, c_double, PD]),
         "hakai_vtk_writer_create": (c_int, [POINTER(c_void_p), c_char_p, c_int64, PD, c_int64, PI64, c_int]),
         "hakai_vtk_writer_submit": (c_int, [c_void_p, c_int, PI64, PD, PD, PD, PD, PD, PD, PD]),
         "hakai_vtk_writer_acquire": (c_int, [c_void_p, c_void_p]),
@@ -177,6 +189,7 @@ def exported_symbols() -> list[str]:
         "hakai_history_enable", "hakai_history_disable", "hakai_history_count", "hakai_history_read",
         "hakai_history_write_csv", "hakai_history_combine", "hakai_inp_history_sets",
         "hakai_stable_dt", "hakai_stable_dt_combine", "hakai_stable_dt_write_csv",
+        "hakai_set_loads", "hakai_clear_loads", "hakai_load_force",
     ]
 
 

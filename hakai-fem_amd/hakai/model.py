@@ -14,7 +14,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _abi
-from ._abi import BCT, MaterialT, check, lib, ptr
+from ._abi import BCT, LoadsT, MaterialT, check, lib, ptr
 
 
 @dataclass
@@ -34,6 +34,62 @@ class BCGroup:
     entries: list  # [(dofs int64 1-based, value float)]
     amp_time: np.ndarray | None = None
     amp_value: np.ndarray | None = None
+
+
+@dataclass
+class Loads:
+    """External loads (hakai_loads_t, include/hakai_hip.h): global 1-based ids. ``amps`` is a list of
+    (time, value) tables of at least two rows; a load's ``*_amp`` is an index into it, -1 the constant 1.
+    ``grav_accel`` is (n_grav, 3), magnitude times direction; ``press_face`` is 1..6 (S1..S6)."""
+    amps: list = field(default_factory=list)
+    cload_dof: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
+    cload_value: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    cload_amp: np.ndarray | None = None
+    grav_accel: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
+    grav_amp: np.ndarray | None = None
+    press_elem: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
+    press_face: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    press_value: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    press_amp: np.ndarray | None = None
+
+    def __post_init__(self):
+        self.amps = [(np.ascontiguousarray(t, np.float64).ravel(), np.ascontiguousarray(v, np.float64).ravel())
+                     for t, v in self.amps]
+        self.cload_dof = np.ascontiguousarray(self.cload_dof, np.int64).ravel()
+        self.cload_value = np.ascontiguousarray(self.cload_value, np.float64).ravel()
+        self.grav_accel = np.ascontiguousarray(self.grav_accel, np.float64).reshape(-1, 3)
+        self.press_elem = np.ascontiguousarray(self.press_elem, np.int64).ravel()
+        self.press_face = np.ascontiguousarray(self.press_face, np.int32).ravel()
+        self.press_value = np.ascontiguousarray(self.press_value, np.float64).ravel()
+        for name, n in (("cload_amp", len(self.cload_dof)), ("grav_amp", len(self.grav_accel)),
+                        ("press_amp", len(self.press_elem))):
+            a = getattr(self, name)
+            a = np.full(n, -1, np.int32) if a is None else np.ascontiguousarray(a, np.int32).ravel()
+            setattr(self, name, a)
+
+    @property
+    def empty(self) -> bool:
+        return len(self.cload_dof) == 0 and len(self.grav_accel) == 0 and len(self.press_elem) == 0
+
+    def c(self):
+        """(LoadsT, holder): keep the holder alive while the C side uses the struct."""
+        i32, i64 = ctypes.c_int32, ctypes.c_int64
+        amp_n = np.array([len(t) for t, _ in self.amps], np.int32)
+        amp_off = np.zeros(len(self.amps), np.int64)
+        if len(self.amps) > 1:
+            amp_off[1:] = np.cumsum(amp_n[:-1])
+        pad = [np.zeros(1)]  # (a pointer even where a list is empty)
+        at = np.ascontiguousarray(np.concatenate([t for t, _ in self.amps] + pad))
+        av = np.ascontiguousarray(np.concatenate([v for _, v in self.amps] + pad))
+        s = LoadsT()
+        s.n_amp, s.amp_n, s.amp_off, s.amp_time, s.amp_value = len(self.amps), ptr(amp_n, i32), ptr(amp_off, i64), \
+            ptr(at), ptr(av)
+        s.n_cload, s.cload_dof, s.cload_value, s.cload_amp = len(self.cload_dof), ptr(self.cload_dof, i64), \
+            ptr(self.cload_value), ptr(self.cload_amp, i32)
+        s.n_grav, s.grav_accel, s.grav_amp = len(self.grav_accel), ptr(self.grav_accel), ptr(self.grav_amp, i32)
+        s.n_press, s.press_elem, s.press_face, s.press_value, s.press_amp = len(self.press_elem), \
+            ptr(self.press_elem, i64), ptr(self.press_face, i32), ptr(self.press_value), ptr(self.press_amp, i32)
+        return s, (amp_n, amp_off, at, av, self)
 
 
 @dataclass
@@ -60,6 +116,8 @@ class Model:
     # read_inp: the drivers' history sets of the deck (hakai_inp_history_sets) -- (names with "all"
     # first, [global 1-based node ids per kept set], names left out); None for a model built in code
     history_sets: tuple | None = None
+    # external loads (*Cload, *Dload, *Dsload of a deck; Solver applies them); None = no loads
+    loads: Loads | None = None
 
     def c_contact_pairs(self):
         """(n_cp, cp_instance int32[2n], cp_elem_off int64[2n+1], cp_elems int64[]) for the C ABI."""
@@ -228,8 +286,21 @@ def read_inp(path: str) -> Model:
                                        len(hnodes), text, cap, ctypes.byref(nd)))
         hnames = text.value.decode().split("\n")[:-1]
         hsets = [hnodes[hoff[s]:hoff[s + 1]].copy() for s in range(ns.value)]
+        ld, loads = m.loads, None
+        if ld.n_cload or ld.n_grav or ld.n_press:
+            lo = _arr(ld.amp_off, ld.n_amp, np.int64)
+            ln = _arr(ld.amp_n, ld.n_amp, np.int32)
+            n_amp = int(max([lo[a] + ln[a] for a in range(ld.n_amp)] + [0]))
+            lt, lv = _arr(ld.amp_time, n_amp, np.float64), _arr(ld.amp_value, n_amp, np.float64)
+            loads = Loads([(lt[lo[a]:lo[a] + ln[a]].copy(), lv[lo[a]:lo[a] + ln[a]].copy()) for a in range(ld.n_amp)],
+                          _arr(ld.cload_dof, ld.n_cload, np.int64), _arr(ld.cload_value, ld.n_cload, np.float64),
+                          _arr(ld.cload_amp, ld.n_cload, np.int32),
+                          _arr(ld.grav_accel, 3 * ld.n_grav, np.float64).reshape(-1, 3),
+                          _arr(ld.grav_amp, ld.n_grav, np.int32), _arr(ld.press_elem, ld.n_press, np.int64),
+                          _arr(ld.press_face, ld.n_press, np.int32), _arr(ld.press_value, ld.n_press, np.float64),
+                          _arr(ld.press_amp, ld.n_press, np.int32))
         return Model(coord, elem, emat, mats, bc, ic_d, ic_v, m.d_time, m.end_time, m.mass_scaling,
                      m.contact_flag, einst, name=str(path), contact_pairs=cps,
-                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]))
+                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]), loads=loads)
     finally:
         L.hakai_inp_free(out)

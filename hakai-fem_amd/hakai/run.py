@@ -230,6 +230,9 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
     """HAKAI(fname) over torch.distributed's world (one process per GPU, already initialised with the
     nccl backend), or over `local_ranks` contexts of one process on `device`."""
     glob = read_inp(fname)
+    if glob.loads is not None and not glob.loads.empty:
+        raise ValueError(f"{fname}: the deck has external loads (*Cload / *Dload / *Dsload); the N-GPU driver does "
+                         "not apply loads yet -- run it on one GPU (hakai.hakai / the hakai CLI)")
     gdiag, _ = glob.lumped_mass()
     dt = glob.dt
     time_num = glob.end_time / dt

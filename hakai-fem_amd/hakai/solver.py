@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._abi import StableDtT, StateT, check, lib, ptr
-from .model import Model
+from .model import Loads, Model
 
 I64 = ctypes.c_int64
 
@@ -78,6 +78,8 @@ class Solver:
                                               ptr(cpi, ctypes.c_int32), ptr(cpo, I64), ptr(cpe, I64)))
             if getattr(model, "contact_params", None) is not None:
                 check(self.L.hakai_set_contact_params(self.ctx, *[float(x) for x in model.contact_params]))
+        if getattr(model, "loads", None) is not None and not model.loads.empty:
+            self.set_loads(model.loads)
         self.reset()
 
     # -- lifecycle ---------------------------------------------------------------------------
@@ -173,6 +175,24 @@ class Solver:
         f = np.zeros(3 * self.model.nNode)
         check(self.L.hakai_contact_force(self.ctx, float(t), float(self.model.dt if d_time is None else d_time),
                                          ptr(f)))
+        return f
+
+    # -- external loads -----------------------------------------------------------------------------
+    def set_loads(self, loads: Loads):
+        """Replace the external loads (hakai_set_loads): concentrated forces, gravity, follower face
+        pressure, each with an optional amplitude table. Captured step graphs are dropped and an
+        enabled history restarts. A refused call leaves the previous loads in force."""
+        s, keep = loads.c()
+        check(self.L.hakai_set_loads(self.ctx, ctypes.byref(s)))
+        del keep
+
+    def clear_loads(self):
+        check(self.L.hakai_clear_loads(self.ctx))
+
+    def load_force(self, t: float, d_time: float | None = None) -> np.ndarray:
+        """The load force of step t at the current device state, without contact (3nN; no step)."""
+        f = np.zeros(3 * self.model.nNode)
+        check(self.L.hakai_load_force(self.ctx, float(t), float(self.model.dt if d_time is None else d_time), ptr(f)))
         return f
 
     # -- profiling (HIP events on the context's own stream) ------------------------------------

@@ -169,6 +169,10 @@ struct Owned {
     std::vector<int64_t> inst_noff, inst_eoff, inst_ne;
     std::vector<int32_t> cp_inst;           // *Contact Pair: 2 instances per pair
     std::vector<int64_t> cp_off, cp_elems;  // surface element lists (instance-local, 1-based)
+    // external loads (*Cload, *Dload, *Dsload), what pub.loads points to
+    std::vector<int32_t> ld_amp_n, ld_cl_amp, ld_g_amp, ld_pr_face, ld_pr_amp;
+    std::vector<int64_t> ld_amp_off, ld_cl_dof, ld_pr_elem;
+    std::vector<double> ld_amp_t, ld_amp_v, ld_cl_val, ld_g_acc, ld_pr_val;
 };
 
 void read_lines(const char* path, std::vector<std::string>& lines) {
@@ -601,11 +605,14 @@ void parse(const char* path, Owned& o) {
             contact_flag = 2;
             break;
         }
-    // ---- *Surface (:517-564): element sets (face ids ignored), instance of the last listed elset
+    // ---- *Surface (:517-564): element sets, instance of the last listed elset. The contact path
+    // takes the elements only; the face id of each "elset, Sk" line is kept next to them for *Dsload
+    // (global element, face 1..6; 0 where the line names no S1..S6), in line order.
     struct Surf {
         std::string name;
         int instance_id = 0;
         std::vector<long long> elements;
+        std::vector<std::pair<long long, int>> faces;
     };
     std::vector<Surf> SURF;
     for (long long i = 1; i <= n; ++i) {
@@ -614,11 +621,18 @@ void parse(const char* path, Owned& o) {
         sf.name = after(at(split(nospace(line(i)), ',', false), 3), "name=");
         for (long long r = i + 1; r <= n; ++r) {
             if (has(line(r), "*")) break;
-            const std::string es = at(split(nospace(line(r)), ',', false), 1);
+            const auto st = split(nospace(line(r)), ',', false);
+            const std::string es = at(st, 1);
+            int face = 0;
+            if (st.size() >= 2 && st[1].size() == 2 && st[1][0] == 'S' && st[1][1] >= '1' && st[1][1] <= '6')
+                face = st[1][1] - '0';
             for (auto& E : ELSET)
                 if (E.name == es) {
                     sf.instance_id = E.instance_id;
                     sf.elements.insert(sf.elements.end(), E.elements.begin(), E.elements.end());
+                    if (E.instance_id > 0)
+                        for (long long el : E.elements)
+                            sf.faces.push_back({el + INST[E.instance_id - 1].element_offset, face});
                 }
         }
         std::sort(sf.elements.begin(), sf.elements.end());
@@ -643,6 +657,112 @@ void parse(const char* path, Owned& o) {
             o.cp_off.push_back((int64_t)o.cp_elems.size());
         }
     }
+
+    // ---- external loads: *Cload, *Dload (GRAV, Pn), *Dsload (P), in deck order. Not in the
+    // reference; an unknown load type, surface, set or amplitude is an error, never a silent skip.
+    auto load_amp = [&](const std::string& head) -> int32_t {  // table index of "amplitude=NAME", -1 without
+        std::string name;
+        for (auto& tok : split(nospace(head), ',', false))
+            if (has(tok, "amplitude=")) name = after(tok, "amplitude=");
+        if (name.empty()) return -1;
+        const Amp* hit = nullptr;
+        for (auto& a : AMP)
+            if (a.name == name) {
+                hit = &a;
+                break;
+            }
+        if (!hit) throw ParseError{"load: unknown amplitude " + name};
+        // one table per use (tables are small; equal names give equal tables)
+        o.ld_amp_n.push_back((int32_t)hit->time.size());
+        o.ld_amp_off.push_back((int64_t)o.ld_amp_t.size());
+        o.ld_amp_t.insert(o.ld_amp_t.end(), hit->time.begin(), hit->time.end());
+        o.ld_amp_v.insert(o.ld_amp_v.end(), hit->value.begin(), hit->value.end());
+        return (int32_t)o.ld_amp_n.size() - 1;
+    };
+    auto is_int = [](const std::string& s) {
+        if (s.empty()) return false;
+        for (char ch : s)
+            if (!std::isdigit((unsigned char)ch)) return false;
+        return true;
+    };
+    for (long long li = 1; li <= n; ++li) {
+        const bool cl = has(line(li), "*Cload"), dl = has(line(li), "*Dload"), ds = has(line(li), "*Dsload");
+        if (!cl && !dl && !ds) continue;
+        const int32_t amp = load_amp(line(li));
+        for (long long i = li + 1; i <= n; ++i) {
+            if (has(line(i), "*")) break;
+            const auto t = split(nospace(line(i)), ',', true);
+            if (t.size() == 1 && t[0].empty()) continue;
+            if (cl) {  // set-or-node, dof, value
+                if (t.size() != 3) throw ParseError{"*Cload: expected 'set-or-node, dof, value': " + line(i)};
+                std::vector<long long> nodes = nodes_of(t[0], true);
+                if (nodes.empty() && is_int(t[0])) nodes.push_back(parse_i(t[0]));
+                if (nodes.empty() && has(t[0], ".")) {  // Instance.node
+                    const auto sss = split(t[0], '.', false);
+                    for (auto& I : INST)
+                        if (sss.size() == 2 && I.name == sss[0] && is_int(sss[1])) {
+                            const long long q = parse_i(sss[1]);
+                            if (q < 1 || q > I.nNode) throw ParseError{"*Cload: node out of range: " + t[0]};
+                            nodes.push_back(q + I.node_offset);
+                        }
+                }
+                if (nodes.empty()) throw ParseError{"*Cload: unknown node set " + t[0]};
+                const long long dir = parse_i(t[1]);
+                const double value = parse_f(t[2]);
+                if (dir < 1) throw ParseError{"*Cload: direction " + t[1]};
+                if (dir > 3) continue;  // rotational dofs: ignored, as *Boundary does
+                for (long long q : nodes) {
+                    if (q < 1 || q > nNode) throw ParseError{"*Cload: node out of range: " + t[0]};
+                    o.ld_cl_dof.push_back(q * 3 - (3 - dir));
+                    o.ld_cl_val.push_back(value);
+                    o.ld_cl_amp.push_back(amp);
+                }
+            } else if (dl) {  // , GRAV, g, nx, ny, nz   |   ELSET, Pn, value
+                if (t.size() < 2) throw ParseError{"*Dload: " + line(i)};
+                if (t[1] == "GRAV") {
+                    if (!t[0].empty()) throw ParseError{"*Dload: GRAV on an element set is not supported: " + t[0]};
+                    if (t.size() != 6) throw ParseError{"*Dload: expected ', GRAV, g, nx, ny, nz': " + line(i)};
+                    const double g = parse_f(t[2]);
+                    for (int c = 0; c < 3; ++c) o.ld_g_acc.push_back(g * parse_f(t[3 + c]));
+                    o.ld_g_amp.push_back(amp);
+                } else if (t[1].size() == 2 && t[1][0] == 'P' && t[1][1] >= '1' && t[1][1] <= '6') {
+                    if (t.size() != 3) throw ParseError{"*Dload: expected 'ELSET, Pn, value': " + line(i)};
+                    const double value = parse_f(t[2]);
+                    bool found = false;
+                    for (auto& E : ELSET)
+                        if (E.name == t[0] && E.instance_id > 0) {
+                            found = true;
+                            for (long long el : E.elements) {
+                                o.ld_pr_elem.push_back(el + INST[E.instance_id - 1].element_offset);
+                                o.ld_pr_face.push_back(t[1][1] - '0');
+                                o.ld_pr_val.push_back(value);
+                                o.ld_pr_amp.push_back(amp);
+                            }
+                        }
+                    if (!found) throw ParseError{"*Dload: unknown element set " + t[0]};
+                } else {
+                    throw ParseError{"*Dload: unknown load type " + t[1]};
+                }
+            } else {  // SURFACE, P, value
+                if (t.size() != 3) throw ParseError{"*Dsload: expected 'SURFACE, P, value': " + line(i)};
+                if (t[1] != "P") throw ParseError{"*Dsload: unknown load type " + t[1]};
+                const double value = parse_f(t[2]);
+                const Surf* hit = nullptr;
+                for (auto& sf : SURF)
+                    if (sf.name == t[0]) hit = &sf;
+                if (!hit) throw ParseError{"*Dsload: unknown surface " + t[0]};
+                for (auto& ef : hit->faces) {
+                    if (ef.second == 0) throw ParseError{"*Dsload: surface " + t[0] + " has a line without a face S1..S6"};
+                    o.ld_pr_elem.push_back(ef.first);
+                    o.ld_pr_face.push_back(ef.second);
+                    o.ld_pr_val.push_back(value);
+                    o.ld_pr_amp.push_back(amp);
+                }
+            }
+        }
+    }
+    for (long long el : o.ld_pr_elem)
+        if (el < 1 || el > nElement) throw ParseError{"load: element out of range"};
 
     // ---- flatten into the C view
     o.coord = coordmat;
@@ -727,6 +847,23 @@ void parse(const char* path, Owned& o) {
     p.instance_node_offset = o.inst_noff.data();
     p.instance_element_offset = o.inst_eoff.data();
     p.instance_nElement = o.inst_ne.data();
+    p.loads.n_amp = (int32_t)o.ld_amp_n.size();
+    p.loads.amp_n = o.ld_amp_n.data();
+    p.loads.amp_off = o.ld_amp_off.data();
+    p.loads.amp_time = o.ld_amp_t.data();
+    p.loads.amp_value = o.ld_amp_v.data();
+    p.loads.n_cload = (int64_t)o.ld_cl_dof.size();
+    p.loads.cload_dof = o.ld_cl_dof.data();
+    p.loads.cload_value = o.ld_cl_val.data();
+    p.loads.cload_amp = o.ld_cl_amp.data();
+    p.loads.n_grav = (int32_t)o.ld_g_amp.size();
+    p.loads.grav_accel = o.ld_g_acc.data();
+    p.loads.grav_amp = o.ld_g_amp.data();
+    p.loads.n_press = (int64_t)o.ld_pr_elem.size();
+    p.loads.press_elem = o.ld_pr_elem.data();
+    p.loads.press_face = o.ld_pr_face.data();
+    p.loads.press_value = o.ld_pr_val.data();
+    p.loads.press_amp = o.ld_pr_amp.data();
 }
 
 void pusai_table(double P[8][3][8]) {  // cal_Pusai_hexa, v2/HAKAI_j.jl:1895-1943
@@ -850,6 +987,8 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
     if ((r = hakai_set_bc(c, &M->bc))) return r;
     if (M->contact_flag >= 1 && (r = hakai_set_contact_cp(c, M->contact_flag, M->element_instance, M->n_cp,
                                                           M->cp_instance, M->cp_elem_off, M->cp_elems)))
+        return r;
+    if ((M->loads.n_cload > 0 || M->loads.n_grav > 0 || M->loads.n_press > 0) && (r = hakai_set_loads(c, &M->loads)))
         return r;
     if ((r = hakai_reset_state(c, M->n_ic_dofs, M->ic_dofs, M->ic_values, d_time))) return r;
     const long long n_steps = time_num >= 1.0 ? (long long)std::floor(time_num) : 0;

@@ -218,7 +218,8 @@ int hakai_set_tuning(hakai_ctx* ctx, const char* key, int64_t value);
  * force assembled from u_k (what step k+1's nodal update consumes), du_k = u_k - u_{k-1},
  * c_k = (du_{k+1} + du_k) / 2. Step t = k+1 sums, per set:
  *    0-2  F_int[c]  Q_k (the reaction force on a clamped set)
- *    3-5  F_ext[c]  f_k (0 without contact)
+ *    3-5  F_ext[c]  f_k (0 without contact and loads; with hakai_set_loads the step's total external
+ *                   force, contact plus loads, so W_ext is their work and the identity below holds)
  *    6-8  P[c]      m du_{k+1} / dt
  *    9    KE        1/2 m sum_c (du_{k+1} / dt)^2 (the velocity a download after this step reports)
  *   10    W_int     accumulated since the (re)start: += sum_c Q_k c_k
@@ -332,6 +333,72 @@ int hakai_stable_dt_combine(int32_t n_ranks, const hakai_stable_dt_t* parts, hak
 int hakai_stable_dt_write_csv(const char* path, int64_t n, const int64_t* steps, const hakai_stable_dt_t* rec,
                               double d_time);
 
+/* ---- external loads: nodal forces, gravity and follower face pressure ------------------------- */
+/* The reference has no loads: nothing here has a counterpart in it. With loads set, every hakai_step
+ * (captured graphs included) forms, in one launch after the contact search and before the nodal
+ * update, the step's total external force: per node and component, every addition rounded once,
+ *     the contact force of the step (+0.0 without contact)
+ *   + the node's concentrated entries, value * amp, in list order
+ *   + the gravity entries, mass[n] * (grav_accel[c] * amp), in list order (all three components)
+ *   + the node's pressure contributions, in ascending order of the press_* index.
+ * That total is what the nodal update, the multi-GPU interface fix and the history output take as
+ * the external force (history's F_ext / W_ext are then contact plus loads). A node without any load
+ * gets the contact force (or zero) unchanged. Without loads nothing is launched or allocated.
+ *
+ * Amplitude tables: n_amp tables, table a holds amp_n[a] >= 2 rows (time, value) at amp_off[a]. A
+ * load names a table by index; -1 is the constant 1. The value at ct = t * d_time (in a captured
+ * graph (*t_rd + 1.0) * dt from the device step counter, the same expression) follows the rule of
+ * the *Boundary amplitudes: the first segment j with time[j] <= ct <= time[j+1], linearly
+ * interpolated; if none matches, the first segment extrapolated.
+ * Concentrated loads: cload_dof (1-based dofs), cload_value, cload_amp; several entries on a dof add.
+ * Gravity: grav_accel[3 n_grav] (magnitude times direction) acts on the whole model through the
+ * uploaded diag_M, so a mass-scaled model keeps the acceleration.
+ * Pressure: press_elem (1-based), press_face (1..6), press_value, press_amp. A follower load: it is
+ * evaluated every step on the current configuration coord + disp (the displacement the nodal update
+ * reads), and only while the face's element is active (element_flag == 1). Faces in terms of the
+ * elementmat columns 1..8: S1 = 1-2-3-4, S2 = 5-8-7-6, S3 = 1-5-6-2, S4 = 2-6-7-3, S5 = 3-7-8-4,
+ * S6 = 4-8-5-1; on a non-inverted element a positive pressure pushes every face into the element
+ * (a unit cube's face gets -p A n_out in total). With corners x0..x3 in that order, (xi_a, eta_a) =
+ * (-,-), (+,-), (+,+), (-,+), g1 = (-x0+x1+x2-x3)/4, g2 = (-x0-x1+x2+x3)/4, h = (x0-x1+x2-x3)/4:
+ *     F_a = (p amp) [ g1 x g2 + (xi_a / 3) g1 x h + (eta_a / 3) h x g2 ],
+ * the exact integral of N_a (dx/dxi x dx/deta); the four sum to p times the face's area vector.
+ * csrc/hakai_loads_face.hpp is the one definition of the operation order.
+ *
+ * hakai_set_loads replaces the loads (the arrays are copied). HAKAI_ERR_ARG changes nothing and
+ * leaves the previous loads in force: a dof or element out of range, a face outside 1..6, an
+ * amplitude index out of range, a table with fewer than two rows, a non-finite value, a negative
+ * count. HAKAI_ERR_STATE: before hakai_upload_model; pressure on a context with a communicator (a
+ * face across a cut needs nodes the rank does not hold). On such a context concentrated loads and
+ * gravity are accepted: every rank gives the full load of each of its local nodes, shared nodes
+ * included, with local ids, and the result is bit-identical to one context.
+ * hakai_upload_model clears the loads; hakai_set_bc, hakai_reset_state and hakai_upload_state keep
+ * them. hakai_set_loads and hakai_clear_loads drop captured step graphs and, with history enabled,
+ * restart the history like a state upload (W_ext changes its meaning).
+ * hakai_load_force is a probe like hakai_contact_force: the load force (3nN, without contact) of
+ * step t at the current state, no step; zeros without loads. */
+typedef struct {
+    int32_t n_amp;
+    const int32_t* amp_n;       /* [n_amp] rows per table (>= 2) */
+    const int64_t* amp_off;     /* [n_amp] into amp_time / amp_value */
+    const double* amp_time;
+    const double* amp_value;
+    int64_t n_cload;
+    const int64_t* cload_dof;   /* [n_cload] 1-based dofs */
+    const double* cload_value;  /* [n_cload] */
+    const int32_t* cload_amp;   /* [n_cload] table index, -1: constant 1 */
+    int32_t n_grav;
+    const double* grav_accel;   /* [3 n_grav] */
+    const int32_t* grav_amp;    /* [n_grav] */
+    int64_t n_press;
+    const int64_t* press_elem;  /* [n_press] 1-based elements */
+    const int32_t* press_face;  /* [n_press] 1..6 */
+    const double* press_value;  /* [n_press] */
+    const int32_t* press_amp;   /* [n_press] */
+} hakai_loads_t;
+int hakai_set_loads(hakai_ctx* ctx, const hakai_loads_t* loads);
+int hakai_clear_loads(hakai_ctx* ctx);
+int hakai_load_force(hakai_ctx* ctx, double t, double d_time, double* load_force);
+
 /* ---- contact: all-exterior instance-vs-instance penalty contact --------- */
 /* Enables contact for the uploaded model: contact_flag as readInpFile sets it (1 = *Contact,
  * 2 = HAKAIoption=self-contact; v2/readInpFile_j.jl:1046-1060), element_instance = instance
@@ -437,6 +504,11 @@ typedef struct {
     const int32_t* cp_instance;             /* [2 n_cp] instances (1-based) of the two surfaces */
     const int64_t* cp_elem_off;             /* [2 n_cp + 1] into cp_elems */
     const int64_t* cp_elems;                /* surface elements, instance-local 1-based */
+    /* *Cload, *Dload (GRAV on the whole model, Pn on an element set) and *Dsload (P on a *Surface),
+     * each with an optional amplitude=NAME; global ids; the arrays are owned by the model. A deck
+     * without these keywords has every count 0. An unknown load type, surface, set or amplitude is a
+     * parse error. */
+    hakai_loads_t loads;
 } hakai_inp_model_t;
 
 int hakai_inp_read(const char* path, hakai_inp_model_t** out);
@@ -493,7 +565,8 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
  * mass_scaling, the stepped d_time = increment * sqrt(mass_scaling)) and writes
  * out_dir/stable_dt.csv (hakai_stable_dt_write_csv) at the end; verbose: one stderr line the first
  * time d_time > dt_est and one the first time d_time > dt_safe, each naming the element. The VTK
- * files and stdout are the same bytes with and without; unset, nothing changes. */
+ * files and stdout are the same bytes with and without; unset, nothing changes.
+ * The deck's loads (hakai_inp_model_t::loads) are applied with hakai_set_loads. */
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose);
 /* The sets of that history output, for another driver of the same deck (the N-GPU driver, hakai.run):
  * n_sets (without set 0), set_off[n_sets+1] (room for 16) into set_nodes (global 1-based ids;

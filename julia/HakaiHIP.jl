@@ -298,6 +298,14 @@ set_contact_params(c::Ctx; myu = 0.25, kc_o = 1.0, kc_s = 1.0, Cr_o = 0.0, Cr_s 
 contact_force!(c::Ctx, external_force, t, d_time) =
     check(ccall((:hakai_contact_force, lib), Cint, (Ptr{Cvoid}, Float64, Float64, Ptr{Float64}),
                 c.p, t, d_time, external_force))
+# External loads (include/hakai_hip.h, "external loads"): load_force! is the probe next to
+# contact_force! (the load force of step t at the current state, without contact), clear_loads drops
+# them. Loads are set from a deck by hakai_run_inp; hakai_set_loads takes a hakai_loads_t of flat
+# arrays, which this shim does not mirror yet.
+load_force!(c::Ctx, load_force, t, d_time) =
+    check(ccall((:hakai_load_force, lib), Cint, (Ptr{Cvoid}, Float64, Float64, Ptr{Float64}),
+                c.p, t, d_time, load_force))
+clear_loads(c::Ctx) = check(ccall((:hakai_clear_loads, lib), Cint, (Ptr{Cvoid},), c.p))
 function contact_stats(c::Ctx)
     st = zeros(Int64, 10)
     check(ccall((:hakai_contact_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int32), c.p, st, length(st)))
