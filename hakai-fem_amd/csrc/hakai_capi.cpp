@@ -1002,7 +1002,7 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
         }
         na.fext = c->d_fext;
     }
-    if (c->loads) {  // external loads: contact force + loads -> the step's total external force
+    if (c->loads) {  // external loads, rigid walls: contact force + loads + walls -> the step's total external force
         if ((rc = hkc::loads_step(c, t, d_time, na.fext))) return rc;
         na.fext = c->d_ftot;  // = hkc::step_fext(c), what the interface fix takes too
     }

@@ -13,7 +13,7 @@ struct Comm;     // multi-GPU state (hakai_comm.cpp)
 struct Contact;  // contact search state (hakai_contact_state.hpp)
 struct History;  // history output state (hakai_history.hip)
 struct StableDt; // stable-time-step scratch (hakai_stable_dt.hip)
-struct Loads;    // external loads (hakai_loads.hip)
+struct Loads;    // external loads and rigid walls (hakai_loads.hip)
 int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 }  // namespace hkc
@@ -164,8 +164,9 @@ struct hakai_ctx {
     // first call, and the Poisson ratios its material table needs next to h_young
     hkc::StableDt* sdt = nullptr;
     std::vector<double> h_poisson;     // per material
-    // external loads (hakai_set_loads; hakai_loads.hpp): null without loads. d_ftot [3nN] is the
-    // step's total external force, contact plus loads (owned by the loads state)
+    // external loads and rigid walls (hakai_set_loads, hakai_set_walls; hakai_loads.hpp): null without
+    // both. d_ftot [3nN] is the step's total external force, contact plus loads plus walls (owned by
+    // that state)
     hkc::Loads* loads = nullptr;
     double* d_ftot = nullptr;
 };
@@ -173,7 +174,7 @@ struct hakai_ctx {
 
 namespace hkc {
 // The external force every consumer of a step takes (nodal update, interface fix, history): the total
-// of contact and loads where loads are set, else the contact force, else none.
+// of contact, loads and walls where loads or walls are set, else the contact force, else none.
 inline const double* step_fext(const hakai_ctx* c) {
     return c->d_ftot ? c->d_ftot : (c->contact ? c->d_fext : nullptr);
 }

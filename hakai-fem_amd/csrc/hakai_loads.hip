@@ -14,8 +14,17 @@
 // as k_nodal does; which kinds of load exist is a launch-time constant (template parameters), so a
 // node of a gravity-only model runs no list code and no runtime branch joins the loads; the time, the
 // gravity entries and their amplitude tables are uniform over the launch.
+// Rigid walls (hakai_set_walls) join the same sum in the same launch, after the pressure
+// contributions: the fifth template parameter WL (0 no wall: the code of the four-flag kernel,
+// 1 every wall takes every node, 2 a 32-bit membership mask per node). The loop over the walls is
+// wave-uniform: the wall table and the walls' amplitude tables are read at uniform addresses
+// (scalar loads), the wall's frame (two amplitude values, origin, velocity) is formed once per wave,
+// and a lane's own work is the bit test, the gap and, under d > 0, hakai_walls_node.hpp's force. The
+// node's coord, u_k, u_{k-1}, mass and mask are issued with its other operands, before the gathers.
+// Loads and walls are independent parts of one device state that owns d_ftot.
 // Compiled without contraction: the operation order of the header is the definition
-// (tests/loads_ref.py restates it, tests/test_gpu_loads.py compares bit for bit).
+// (tests/loads_ref.py and tests/walls_ref.py restate it, tests/test_gpu_loads.py and
+// tests/test_gpu_walls.py compare bit for bit).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -28,6 +37,8 @@
 #include "hakai_loads.hpp"
 #include "hakai_loads_face.hpp"
 #include "hakai_loads_plan.hpp"
+#include "hakai_walls_node.hpp"
+#include "hakai_walls_plan.hpp"
 
 using hkc::fail;
 using hkc::hip_fail;
@@ -71,6 +82,17 @@ struct LoadArgs {
     const int* pr_code;
     const int* pr_amp;
     const double* pr_val;
+    // rigid walls (appended: the offsets of the fields above are those of the kernel without walls)
+    const double* u_pre;   // [3nN] u_{k-1}, still intact before the nodal update
+    double tau0, taum;     // (t - 1.0) * d_time, (t - 2.0) * d_time; graph mode: from *t_rd
+    int n_wall;
+    const double* w_tab;   // [kWallRow n_wall]
+    const int* w_amp;      // [n_wall]
+    const unsigned* w_mask;  // [nN], WL == 2
+    const int* w_amp_n;
+    const int* w_amp_off;
+    const double* w_amp_t;
+    const double* w_amp_v;
 };
 
 __device__ __forceinline__ double amp_of(const LoadArgs& a, int table, double ct) {
@@ -79,8 +101,9 @@ __device__ __forceinline__ double amp_of(const LoadArgs& a, int table, double ct
     return hk::loads_amp(a.amp_n[table], a.amp_t + off, a.amp_v + off, ct);
 }
 
-// FC: a contact force is added to; CL / GR / PR: concentrated, gravity, pressure entries exist.
-template <bool FC, bool CL, bool GR, bool PR>
+// FC: a contact force is added to; CL / GR / PR: concentrated, gravity, pressure entries exist;
+// WL: walls exist (1: every wall takes every node, 2: per-node mask).
+template <bool FC, bool CL, bool GR, bool PR, int WL>
 __global__ __launch_bounds__(kThreads) void k_loads(LoadArgs a) {
 #pragma clang fp contract(off)
     const long long n = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -89,9 +112,20 @@ __global__ __launch_bounds__(kThreads) void k_loads(LoadArgs a) {
     double f0 = FC ? a.fc[3 * n + 0] : 0.0;
     double f1 = FC ? a.fc[3 * n + 1] : 0.0;
     double f2 = FC ? a.fc[3 * n + 2] : 0.0;
-    const double m = GR ? a.mass[n] : 0.0;
+    const double m = (GR || WL) ? a.mass[n] : 0.0;
     const int c0 = CL ? a.cl_ptr[n] : 0, c1 = CL ? a.cl_ptr[n + 1] : 0;
     const int p0 = PR ? a.pr_ptr[n] : 0, p1 = PR ? a.pr_ptr[n + 1] : 0;
+    double xc[3] = {0.0, 0.0, 0.0}, uk[3] = {0.0, 0.0, 0.0}, um[3] = {0.0, 0.0, 0.0};
+    unsigned wmask = 0xffffffffu;
+    if (WL) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            xc[c] = a.coord[3 * n + c];
+            uk[c] = a.u[3 * n + c];
+            um[c] = a.u_pre[3 * n + c];
+        }
+        if (WL == 2) wmask = a.w_mask[n];
+    }
     const double ct = a.t_rd ? (*a.t_rd + 1.0) * a.dt : a.ct;  // t * d_time, as on the host
     if (CL) {
         for (int j = c0; j < c1; ++j) {
@@ -134,31 +168,64 @@ __global__ __launch_bounds__(kThreads) void k_loads(LoadArgs a) {
             }
         }
     }
+    if (WL) {
+        const double tau0 = a.t_rd ? (*a.t_rd) * a.dt : a.tau0;          // (t - 1.0) * d_time
+        const double taum = a.t_rd ? (*a.t_rd - 1.0) * a.dt : a.taum;    // (t - 2.0) * d_time
+        for (int w = 0; w < a.n_wall; ++w) {  // uniform: scalar loads, one frame per wave
+            const double* row = a.w_tab + hk::kWallRow * w;
+            const int table = a.w_amp[w];
+            double s0 = 1.0, sm = 1.0;
+            if (table >= 0) {
+                const int off = a.w_amp_off[table], nr = a.w_amp_n[table];
+                s0 = hk::loads_amp(nr, a.w_amp_t + off, a.w_amp_v + off, tau0);
+                sm = hk::loads_amp(nr, a.w_amp_t + off, a.w_amp_v + off, taum);
+            }
+            double o[3], vw[3];
+            hk::walls_frame(row + 3, row + 6, s0, sm, a.dt, o, vw);
+            const double d = -hk::walls_gap(xc, uk, o, row);
+            if (((wmask >> w) & 1u) && d > 0.0) {
+                double F[3];
+                hk::walls_force(d, uk, um, m, a.dt, vw, row, row[9], row[10], row[11], row[12], F);
+                f0 = f0 + F[0];
+                f1 = f1 + F[1];
+                f2 = f2 + F[2];
+            }
+        }
+    }
     a.ftot[3 * n + 0] = f0;
     a.ftot[3 * n + 1] = f1;
     a.ftot[3 * n + 2] = f2;
 }
 
-template <bool FC, bool CL, bool GR>
-void launch_pr(const LoadArgs& a, bool pr, unsigned grid, hipStream_t s) {
-    if (pr)
-        hipLaunchKernelGGL((k_loads<FC, CL, GR, true>), dim3(grid), dim3(kThreads), 0, s, a);
+template <bool FC, bool CL, bool GR, bool PR>
+void launch_wl(const LoadArgs& a, int wl, unsigned grid, hipStream_t s) {
+    if (wl == 2)
+        hipLaunchKernelGGL((k_loads<FC, CL, GR, PR, 2>), dim3(grid), dim3(kThreads), 0, s, a);
+    else if (wl == 1)
+        hipLaunchKernelGGL((k_loads<FC, CL, GR, PR, 1>), dim3(grid), dim3(kThreads), 0, s, a);
     else
-        hipLaunchKernelGGL((k_loads<FC, CL, GR, false>), dim3(grid), dim3(kThreads), 0, s, a);
+        hipLaunchKernelGGL((k_loads<FC, CL, GR, PR, 0>), dim3(grid), dim3(kThreads), 0, s, a);
+}
+template <bool FC, bool CL, bool GR>
+void launch_pr(const LoadArgs& a, bool pr, int wl, unsigned grid, hipStream_t s) {
+    if (pr)
+        launch_wl<FC, CL, GR, true>(a, wl, grid, s);
+    else
+        launch_wl<FC, CL, GR, false>(a, wl, grid, s);
 }
 template <bool FC, bool CL>
-void launch_gr(const LoadArgs& a, bool gr, bool pr, unsigned grid, hipStream_t s) {
+void launch_gr(const LoadArgs& a, bool gr, bool pr, int wl, unsigned grid, hipStream_t s) {
     if (gr)
-        launch_pr<FC, CL, true>(a, pr, grid, s);
+        launch_pr<FC, CL, true>(a, pr, wl, grid, s);
     else
-        launch_pr<FC, CL, false>(a, pr, grid, s);
+        launch_pr<FC, CL, false>(a, pr, wl, grid, s);
 }
 template <bool FC>
-void launch_cl(const LoadArgs& a, bool cl, bool gr, bool pr, unsigned grid, hipStream_t s) {
+void launch_cl(const LoadArgs& a, bool cl, bool gr, bool pr, int wl, unsigned grid, hipStream_t s) {
     if (cl)
-        launch_gr<FC, true>(a, gr, pr, grid, s);
+        launch_gr<FC, true>(a, gr, pr, wl, grid, s);
     else
-        launch_gr<FC, false>(a, gr, pr, grid, s);
+        launch_gr<FC, false>(a, gr, pr, wl, grid, s);
 }
 
 template <class T>
@@ -173,20 +240,31 @@ hipError_t upload(std::vector<void*>& owned, const T** d, const std::vector<T>& 
     return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
+void free_all(std::vector<void*>& owned) {
+    for (void* p : owned) (void)hipFree(p);
+    owned.clear();
+}
+
 }  // namespace
 
 namespace hkc {
 
-// Device copy of a plan (hakai_loads_plan.hpp) and the total external force of the step.
+// Device state of the external force: the loads' plan (hakai_loads_plan.hpp), the walls' plan
+// (hakai_walls_plan.hpp) -- either may be absent, not both -- and the total external force of the step.
 struct Loads {
-    std::vector<void*> owned;  // every device allocation below
-    LoadArgs a;                // the plan's pointers; the per-step fields are filled at launch
+    void* ftot = nullptr;                // [3nN], c->d_ftot
+    std::vector<void*> owned_l, owned_w; // the device allocations of the loads / of the walls
+    LoadArgs a;                          // both plans' pointers; the per-step fields are filled at launch
     bool cl = false, gr = false, pr = false;
+    int wl = 0;                          // 0 no wall, 1 every wall takes every node, 2 mask
+    bool has_loads() const { return cl || gr || pr; }
 };
 
 static void loads_free(Loads* L) {
     if (!L) return;
-    for (void* p : L->owned) (void)hipFree(p);
+    free_all(L->owned_l);
+    free_all(L->owned_w);
+    if (L->ftot) (void)hipFree(L->ftot);
     delete L;
 }
 
@@ -195,35 +273,75 @@ void loads_destroy(hakai_ctx* c) {
     (void)hipSetDevice(c->device);
     loads_free(c->loads);
     c->loads = nullptr;
-    c->d_ftot = nullptr;  // (owned by the list above)
+    c->d_ftot = nullptr;  // (owned by the state above)
 }
 
-static int loads_launch(hakai_ctx* c, double t, double d_time, const double* fc, const double* t_rd, hipStream_t s) {
+// The state to add a part to: the context's, or a new one with its d_ftot (null: err is set).
+static Loads* loads_state(hakai_ctx* c, hipError_t* err) {
+    *err = hipSuccess;
+    if (c->loads) return c->loads;
+    Loads* L = new Loads();
+    std::memset(&L->a, 0, sizeof L->a);
+    *err = hipMalloc(&L->ftot, 3 * (size_t)c->nN * sizeof(double));
+    if (*err != hipSuccess) {
+        delete L;
+        return nullptr;
+    }
+    c->loads = L;
+    c->d_ftot = (double*)L->ftot;
+    return L;
+}
+
+// with_loads / with_walls: the parts of the sum to form (a step: both; the probes: one each)
+static int loads_launch(hakai_ctx* c, double t, double d_time, const double* fc, const double* t_rd, hipStream_t s,
+                        bool with_loads, bool with_walls) {
     Loads* L = c->loads;
     LoadArgs a = L->a;
     a.fc = fc;
     a.mass = c->d_mass;
     a.coord = c->d_coord;
     a.u = c->d_u[c->cur];
+    a.u_pre = c->d_u[1 - c->cur];
     a.conn = c->d_conn;
     a.flag = c->d_flag;
     a.ftot = c->d_ftot;
     a.nN = c->nN;
     a.ct = t * d_time;
+    a.tau0 = (t - 1.0) * d_time;
+    a.taum = (t - 2.0) * d_time;
     a.t_rd = t_rd;
     a.dt = d_time;
     const unsigned grid = (unsigned)((c->nN + kThreads - 1) / kThreads);
+    const bool cl = with_loads && L->cl, gr = with_loads && L->gr, pr = with_loads && L->pr;
+    const int wl = with_walls ? L->wl : 0;
     if (fc)
-        launch_cl<true>(a, L->cl, L->gr, L->pr, grid, s);
+        launch_cl<true>(a, cl, gr, pr, wl, grid, s);
     else
-        launch_cl<false>(a, L->cl, L->gr, L->pr, grid, s);
+        launch_cl<false>(a, cl, gr, pr, wl, grid, s);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 int loads_step(hakai_ctx* c, double t, double d_time, const double* fc) {
     if (!c->loads) return 0;
-    return loads_launch(c, t, d_time, fc, c->g_trd, c->stream);
+    return loads_launch(c, t, d_time, fc, c->g_trd, c->stream, true, true);
+}
+
+// A probe: one part of the sum alone, at the current state. d_ftot is rewritten whole by every step
+// before anything reads it: the probe may use it.
+static int loads_probe(hakai_ctx* c, double t, double d_time, double* f, bool walls, const char* what) {
+    if (!c || !f) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->state_ok) return fail(HAKAI_ERR_STATE, "%s without state", what);
+    const size_t fn = 3 * (size_t)c->nN;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->loads || (walls ? c->loads->wl == 0 : !c->loads->has_loads())) {
+        for (size_t i = 0; i < fn; ++i) f[i] = 0.0;
+        return 0;
+    }
+    if (int r = loads_launch(c, t, d_time, nullptr, nullptr, c->stream, !walls, walls)) return r;
+    HIPCHK(hipMemcpyAsync(f, c->d_ftot, fn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 }  // namespace hkc
@@ -234,10 +352,16 @@ int hakai_clear_loads(hakai_ctx* c) {
     if (c) hkc::graph_invalidate(c);  // the launch sequence changes
     if (!c) return fail(HAKAI_ERR_ARG, "null");
     if (!c->model_ok) return fail(HAKAI_ERR_STATE, "clear_loads before upload_model");
-    if (!c->loads) return 0;
+    if (!c->loads || !c->loads->has_loads()) return 0;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    hkc::loads_destroy(c);
+    hkc::Loads* L = c->loads;
+    if (L->wl == 0) {
+        hkc::loads_destroy(c);
+    } else {  // the walls stay in force
+        free_all(L->owned_l);
+        L->cl = L->gr = L->pr = false;
+    }
     return hkc::history_restart(c);  // W_ext changes its meaning
 }
 
@@ -255,57 +379,106 @@ int hakai_set_loads(hakai_ctx* c, const hakai_loads_t* in) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIPCHK(hipStreamSynchronize(s));
-    hkc::Loads* L = new hkc::Loads();
-    std::memset(&L->a, 0, sizeof L->a);
-    LoadArgs& a = L->a;
-    void* ftot = nullptr;
-    hipError_t e = hipMalloc(&ftot, 3 * (size_t)c->nN * sizeof(double));
-    if (e == hipSuccess) L->owned.push_back(ftot);
-    if (e == hipSuccess) e = upload(L->owned, &a.amp_n, P.amp_n, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.amp_off, P.amp_off, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.amp_t, P.amp_t, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.amp_v, P.amp_v, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.cl_ptr, P.cl_ptr, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.cl_comp, P.cl_comp, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.cl_amp, P.cl_amp, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.cl_val, P.cl_val, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.g_acc, P.g_acc, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.g_amp, P.g_amp, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.pr_ptr, P.pr_ptr, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.pr_ent, P.pr_ent, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.pr_elem, P.pr_elem, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.pr_code, P.pr_code, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.pr_amp, P.pr_amp, s);
-    if (e == hipSuccess) e = upload(L->owned, &a.pr_val, P.pr_val, s);
+    std::vector<void*> owned;
+    LoadArgs a;
+    std::memset(&a, 0, sizeof a);
+    hipError_t e = upload(owned, &a.amp_n, P.amp_n, s);
+    if (e == hipSuccess) e = upload(owned, &a.amp_off, P.amp_off, s);
+    if (e == hipSuccess) e = upload(owned, &a.amp_t, P.amp_t, s);
+    if (e == hipSuccess) e = upload(owned, &a.amp_v, P.amp_v, s);
+    if (e == hipSuccess) e = upload(owned, &a.cl_ptr, P.cl_ptr, s);
+    if (e == hipSuccess) e = upload(owned, &a.cl_comp, P.cl_comp, s);
+    if (e == hipSuccess) e = upload(owned, &a.cl_amp, P.cl_amp, s);
+    if (e == hipSuccess) e = upload(owned, &a.cl_val, P.cl_val, s);
+    if (e == hipSuccess) e = upload(owned, &a.g_acc, P.g_acc, s);
+    if (e == hipSuccess) e = upload(owned, &a.g_amp, P.g_amp, s);
+    if (e == hipSuccess) e = upload(owned, &a.pr_ptr, P.pr_ptr, s);
+    if (e == hipSuccess) e = upload(owned, &a.pr_ent, P.pr_ent, s);
+    if (e == hipSuccess) e = upload(owned, &a.pr_elem, P.pr_elem, s);
+    if (e == hipSuccess) e = upload(owned, &a.pr_code, P.pr_code, s);
+    if (e == hipSuccess) e = upload(owned, &a.pr_amp, P.pr_amp, s);
+    if (e == hipSuccess) e = upload(owned, &a.pr_val, P.pr_val, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // the plan's vectors go out of scope
-    if (e != hipSuccess) {
-        hkc::loads_free(L);
+    hkc::Loads* L = e == hipSuccess ? hkc::loads_state(c, &e) : nullptr;
+    if (!L) {
+        free_all(owned);
         return hip_fail(e, "set_loads: device copy of the plan");
     }
-    a.n_grav = (int)P.g_amp.size();
+    free_all(L->owned_l);
+    L->owned_l.swap(owned);
+    LoadArgs& d = L->a;
+    d.amp_n = a.amp_n, d.amp_off = a.amp_off, d.amp_t = a.amp_t, d.amp_v = a.amp_v;
+    d.cl_ptr = a.cl_ptr, d.cl_comp = a.cl_comp, d.cl_amp = a.cl_amp, d.cl_val = a.cl_val;
+    d.g_acc = a.g_acc, d.g_amp = a.g_amp, d.n_grav = (int)P.g_amp.size();
+    d.pr_ptr = a.pr_ptr, d.pr_ent = a.pr_ent, d.pr_elem = a.pr_elem, d.pr_code = a.pr_code, d.pr_amp = a.pr_amp,
+    d.pr_val = a.pr_val;
     L->cl = !P.cl_ptr.empty();
-    L->gr = a.n_grav > 0;
+    L->gr = d.n_grav > 0;
     L->pr = !P.pr_ptr.empty();
-    hkc::loads_destroy(c);
-    c->loads = L;
-    c->d_ftot = (double*)ftot;
     return hkc::history_restart(c);  // W_ext changes its meaning
 }
 
 int hakai_load_force(hakai_ctx* c, double t, double d_time, double* f) {
-    if (!c || !f) return fail(HAKAI_ERR_ARG, "null");
-    if (!c->state_ok) return fail(HAKAI_ERR_STATE, "load_force without state");
-    const size_t fn = 3 * (size_t)c->nN;
+    return hkc::loads_probe(c, t, d_time, f, false, "load_force");
+}
+
+int hakai_clear_walls(hakai_ctx* c) {
+    if (c) hkc::graph_invalidate(c);  // the launch sequence changes
+    if (!c) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->model_ok) return fail(HAKAI_ERR_STATE, "clear_walls before upload_model");
+    if (!c->loads || c->loads->wl == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    if (!c->loads) {
-        for (size_t i = 0; i < fn; ++i) f[i] = 0.0;
-        return 0;
-    }
-    // d_ftot is rewritten whole by every step before anything reads it: the probe may use it
-    if (int r = hkc::loads_launch(c, t, d_time, nullptr, nullptr, c->stream)) return r;
-    HIPCHK(hipMemcpyAsync(f, c->d_ftot, fn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    hkc::Loads* L = c->loads;
+    if (!L->has_loads()) {
+        hkc::loads_destroy(c);
+    } else {  // the loads stay in force
+        free_all(L->owned_w);
+        L->wl = 0;
+        L->a.n_wall = 0;
+    }
+    return hkc::history_restart(c);  // W_ext changes its meaning
+}
+
+int hakai_set_walls(hakai_ctx* c, const hakai_walls_t* in) {
+    if (c) hkc::graph_invalidate(c);  // the launch sequence changes
+    if (!c || !in) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->model_ok) return fail(HAKAI_ERR_STATE, "set_walls before upload_model");
+    hk::WallsPlan P;
+    std::string err;
+    if (hk::walls_plan(*in, c->nN, P, err)) return fail(HAKAI_ERR_ARG, "%s", err.c_str());
+    if (P.n_wall == 0) return hakai_clear_walls(c);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<void*> owned;
+    LoadArgs a;
+    std::memset(&a, 0, sizeof a);
+    hipError_t e = upload(owned, &a.w_amp_n, P.amp_n, s);
+    if (e == hipSuccess) e = upload(owned, &a.w_amp_off, P.amp_off, s);
+    if (e == hipSuccess) e = upload(owned, &a.w_amp_t, P.amp_t, s);
+    if (e == hipSuccess) e = upload(owned, &a.w_amp_v, P.amp_v, s);
+    if (e == hipSuccess) e = upload(owned, &a.w_tab, P.tab, s);
+    if (e == hipSuccess) e = upload(owned, &a.w_amp, P.amp, s);
+    if (e == hipSuccess) e = upload(owned, &a.w_mask, P.mask, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the plan's vectors go out of scope
+    hkc::Loads* L = e == hipSuccess ? hkc::loads_state(c, &e) : nullptr;
+    if (!L) {
+        free_all(owned);
+        return hip_fail(e, "set_walls: device copy of the plan");
+    }
+    free_all(L->owned_w);
+    L->owned_w.swap(owned);
+    LoadArgs& d = L->a;
+    d.w_amp_n = a.w_amp_n, d.w_amp_off = a.w_amp_off, d.w_amp_t = a.w_amp_t, d.w_amp_v = a.w_amp_v;
+    d.w_tab = a.w_tab, d.w_amp = a.w_amp, d.w_mask = a.w_mask;
+    d.n_wall = P.n_wall;
+    L->wl = P.mask.empty() ? 1 : 2;
+    return hkc::history_restart(c);  // W_ext changes its meaning
+}
+
+int hakai_wall_force(hakai_ctx* c, double t, double d_time, double* f) {
+    return hkc::loads_probe(c, t, d_time, f, true, "wall_force");
 }
 
 }  // extern "C"

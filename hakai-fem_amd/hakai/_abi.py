@@ -71,6 +71,15 @@ class LoadsT(ctypes.Structure):
                 ("press_amp", PI32)]
 
 
+class WallsT(ctypes.Structure):
+    """hakai_walls_t: amplitude tables, then per wall origin, normal, motion, table, penalty, damping,
+    friction and the node list."""
+    _fields_ = [("n_amp", c_int32), ("amp_n", PI32), ("amp_off", PI64), ("amp_time", PD), ("amp_value", PD),
+                ("n_wall", c_int32), ("origin", PD), ("normal", PD), ("motion", PD), ("amp", PI32),
+                ("stiffness", PD), ("scale", PD), ("damping", PD), ("friction", PD),
+                ("node_off", PI64), ("nodes", PI64)]
+
+
 class InpModelT(ctypes.Structure):
     _fields_ = [("nNode", c_int64), ("coordmat", PD), ("nElement", c_int64), ("elementmat", PI64),
                 ("element_material", PI64), ("element_instance", PI64), ("nMat", c_int32),
@@ -79,7 +88,7 @@ class InpModelT(ctypes.Structure):
                 ("n_ic_dofs", c_int64), ("ic_dofs", PI64), ("ic_values", PD), ("n_instance", c_int32),
                 ("instance_node_offset", PI64), ("instance_element_offset", PI64),
                 ("instance_nElement", PI64), ("n_cp", c_int32), ("cp_instance", PI32), ("cp_elem_off", PI64),
-                ("cp_elems", PI64), ("loads", LoadsT)]
+                ("cp_elems", PI64), ("loads", LoadsT), ("walls", WallsT)]
 
 
 class HakaiError(RuntimeError):
@@ -159,6 +168,9 @@ def lib() -> ctypes.CDLL:
         "hakai_set_loads": (c_int, [c_void_p, POINTER(LoadsT)]),
         "hakai_clear_loads": (c_int, [c_void_p]),
         "hakai_load_force": (c_int, [c_void_p, c_double, c_double, PD]),
+        "hakai_set_walls": (c_int, [c_void_p, POINTER(WallsT)]),
+        "hakai_clear_walls": (c_int, [c_void_p]),
+        "hakai_wall_force": (c_int, [c_void_p, c_double, c_double, PD]),
         "hakai_vtk_writer_create": (c_int, [POINTER(c_void_p), c_char_p, c_int64, PD, c_int64, PI64, c_int]),
         "hakai_vtk_writer_submit": (c_int, [c_void_p, c_int, PI64, PD, PD, PD, PD, PD, PD, PD]),
         "hakai_vtk_writer_acquire": (c_int, [c_void_p, c_void_p]),
@@ -190,6 +202,7 @@ def exported_symbols() -> list[str]:
         "hakai_history_write_csv", "hakai_history_combine", "hakai_inp_history_sets",
         "hakai_stable_dt", "hakai_stable_dt_combine", "hakai_stable_dt_write_csv",
         "hakai_set_loads", "hakai_clear_loads", "hakai_load_force",
+        "hakai_set_walls", "hakai_clear_walls", "hakai_wall_force",
     ]
 
 

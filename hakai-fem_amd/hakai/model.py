@@ -14,7 +14,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _abi
-from ._abi import BCT, LoadsT, MaterialT, check, lib, ptr
+from ._abi import BCT, LoadsT, MaterialT, WallsT, check, lib, ptr
 
 
 @dataclass
@@ -93,6 +93,78 @@ class Loads:
 
 
 @dataclass
+class Walls:
+    """Rigid walls (hakai_walls_t, include/hakai_hip.h): up to 32 moving planes with penalty, damping
+    and Coulomb friction. ``origin``, ``normal``, ``motion`` are (n_wall, 3); ``normal`` is any non-zero
+    vector pointing into the half-space the nodes may occupy (the library normalises it). ``amps`` is
+    a list of (time, value) tables of at least two rows and ``amp`` an index into it per wall, -1 the
+    constant 1: the wall is displaced by motion * amp(time). ``nodes`` is one array of global 1-based
+    ids per wall; an empty one (or None) means every node. Defaults as the deck keyword's: stiffness
+    0, scale 0.5, damping 0, friction 0, no motion."""
+    origin: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
+    normal: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
+    motion: np.ndarray | None = None
+    amp: np.ndarray | None = None
+    stiffness: np.ndarray | None = None
+    scale: np.ndarray | None = None
+    damping: np.ndarray | None = None
+    friction: np.ndarray | None = None
+    nodes: list | None = None
+    amps: list = field(default_factory=list)
+
+    def __post_init__(self):
+        self.amps = [(np.ascontiguousarray(t, np.float64).ravel(), np.ascontiguousarray(v, np.float64).ravel())
+                     for t, v in self.amps]
+        self.origin = np.ascontiguousarray(self.origin, np.float64).reshape(-1, 3)
+        self.normal = np.ascontiguousarray(self.normal, np.float64).reshape(-1, 3)
+        n = len(self.origin)
+        self.motion = np.zeros((n, 3)) if self.motion is None else \
+            np.ascontiguousarray(self.motion, np.float64).reshape(-1, 3)
+        self.amp = np.full(n, -1, np.int32) if self.amp is None else np.ascontiguousarray(self.amp, np.int32).ravel()
+        for name, default in (("stiffness", 0.0), ("scale", 0.5), ("damping", 0.0), ("friction", 0.0)):
+            a = getattr(self, name)
+            a = np.full(n, default) if a is None else np.ascontiguousarray(a, np.float64).ravel()
+            setattr(self, name, a)
+        nodes = [None] * n if self.nodes is None else list(self.nodes)
+        self.nodes = [np.zeros(0, np.int64) if x is None else np.ascontiguousarray(x, np.int64).ravel() for x in nodes]
+        for name in ("normal", "motion", "amp", "stiffness", "scale", "damping", "friction", "nodes"):
+            if len(getattr(self, name)) != n:
+                raise ValueError(f"Walls.{name}: {len(getattr(self, name))} entries for {n} walls")
+
+    @property
+    def n_wall(self) -> int:
+        return len(self.origin)
+
+    @property
+    def empty(self) -> bool:
+        return self.n_wall == 0
+
+    def c(self):
+        """(WallsT, holder): keep the holder alive while the C side uses the struct."""
+        i32, i64 = ctypes.c_int32, ctypes.c_int64
+        amp_n = np.array([len(t) for t, _ in self.amps], np.int32)
+        amp_off = np.zeros(len(self.amps), np.int64)
+        if len(self.amps) > 1:
+            amp_off[1:] = np.cumsum(amp_n[:-1])
+        pad = [np.zeros(1)]  # (a pointer even where a list is empty)
+        at = np.ascontiguousarray(np.concatenate([t for t, _ in self.amps] + pad))
+        av = np.ascontiguousarray(np.concatenate([v for _, v in self.amps] + pad))
+        node_off = np.concatenate([[0], np.cumsum([len(x) for x in self.nodes])]).astype(np.int64)
+        nodes = np.ascontiguousarray(np.concatenate(self.nodes + [np.zeros(1, np.int64)]))
+        arrs = [np.ascontiguousarray(np.concatenate([a.ravel(), np.zeros(1, a.dtype)]))
+                for a in (self.origin, self.normal, self.motion, self.amp, self.stiffness, self.scale, self.damping,
+                          self.friction)]
+        s = WallsT()
+        s.n_amp, s.amp_n, s.amp_off, s.amp_time, s.amp_value = len(self.amps), ptr(amp_n, i32), ptr(amp_off, i64), \
+            ptr(at), ptr(av)
+        s.n_wall = self.n_wall
+        s.origin, s.normal, s.motion, s.amp = ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), ptr(arrs[3], i32)
+        s.stiffness, s.scale, s.damping, s.friction = ptr(arrs[4]), ptr(arrs[5]), ptr(arrs[6]), ptr(arrs[7])
+        s.node_off, s.nodes = ptr(node_off, i64), ptr(nodes, i64)
+        return s, (amp_n, amp_off, at, av, node_off, nodes, arrs, self)
+
+
+@dataclass
 class Model:
     coordmat: np.ndarray
     elementmat: np.ndarray
@@ -118,6 +190,8 @@ class Model:
     history_sets: tuple | None = None
     # external loads (*Cload, *Dload, *Dsload of a deck; Solver applies them); None = no loads
     loads: Loads | None = None
+    # rigid walls (*Rigid Wall of a deck; Solver applies them); None = no wall
+    walls: Walls | None = None
 
     def c_contact_pairs(self):
         """(n_cp, cp_instance int32[2n], cp_elem_off int64[2n+1], cp_elems int64[]) for the C ABI."""
@@ -299,8 +373,23 @@ def read_inp(path: str) -> Model:
                           _arr(ld.grav_amp, ld.n_grav, np.int32), _arr(ld.press_elem, ld.n_press, np.int64),
                           _arr(ld.press_face, ld.n_press, np.int32), _arr(ld.press_value, ld.n_press, np.float64),
                           _arr(ld.press_amp, ld.n_press, np.int32))
+        wl, walls = m.walls, None
+        if wl.n_wall:
+            nw = wl.n_wall
+            wo = _arr(wl.amp_off, wl.n_amp, np.int64)
+            wn = _arr(wl.amp_n, wl.n_amp, np.int32)
+            n_amp = int(max([wo[a] + wn[a] for a in range(wl.n_amp)] + [0]))
+            wt, wv = _arr(wl.amp_time, n_amp, np.float64), _arr(wl.amp_value, n_amp, np.float64)
+            noff = _arr(wl.node_off, nw + 1, np.int64)
+            wnodes = _arr(wl.nodes, int(noff[-1]), np.int64)
+            walls = Walls(_arr(wl.origin, 3 * nw, np.float64), _arr(wl.normal, 3 * nw, np.float64),
+                          _arr(wl.motion, 3 * nw, np.float64), _arr(wl.amp, nw, np.int32),
+                          _arr(wl.stiffness, nw, np.float64), _arr(wl.scale, nw, np.float64),
+                          _arr(wl.damping, nw, np.float64), _arr(wl.friction, nw, np.float64),
+                          [wnodes[noff[w]:noff[w + 1]].copy() for w in range(nw)],
+                          [(wt[wo[a]:wo[a] + wn[a]].copy(), wv[wo[a]:wo[a] + wn[a]].copy()) for a in range(wl.n_amp)])
         return Model(coord, elem, emat, mats, bc, ic_d, ic_v, m.d_time, m.end_time, m.mass_scaling,
                      m.contact_flag, einst, name=str(path), contact_pairs=cps,
-                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]), loads=loads)
+                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]), loads=loads, walls=walls)
     finally:
         L.hakai_inp_free(out)

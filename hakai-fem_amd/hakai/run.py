@@ -233,6 +233,9 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
     if glob.loads is not None and not glob.loads.empty:
         raise ValueError(f"{fname}: the deck has external loads (*Cload / *Dload / *Dsload); the N-GPU driver does "
                          "not apply loads yet -- run it on one GPU (hakai.hakai / the hakai CLI)")
+    if glob.walls is not None and not glob.walls.empty:
+        raise ValueError(f"{fname}: the deck has rigid walls (*Rigid Wall); the N-GPU driver does not apply walls "
+                         "yet -- run it on one GPU (hakai.hakai / the hakai CLI)")
     gdiag, _ = glob.lumped_mass()
     dt = glob.dt
     time_num = glob.end_time / dt

@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._abi import StableDtT, StateT, check, lib, ptr
-from .model import Loads, Model
+from .model import Loads, Model, Walls
 
 I64 = ctypes.c_int64
 
@@ -80,6 +80,8 @@ class Solver:
                 check(self.L.hakai_set_contact_params(self.ctx, *[float(x) for x in model.contact_params]))
         if getattr(model, "loads", None) is not None and not model.loads.empty:
             self.set_loads(model.loads)
+        if getattr(model, "walls", None) is not None and not model.walls.empty:
+            self.set_walls(model.walls)
         self.reset()
 
     # -- lifecycle ---------------------------------------------------------------------------
@@ -193,6 +195,24 @@ class Solver:
         """The load force of step t at the current device state, without contact (3nN; no step)."""
         f = np.zeros(3 * self.model.nNode)
         check(self.L.hakai_load_force(self.ctx, float(t), float(self.model.dt if d_time is None else d_time), ptr(f)))
+        return f
+
+    # -- rigid walls ----------------------------------------------------------------------------------
+    def set_walls(self, walls: Walls):
+        """Replace the rigid walls (hakai_set_walls): moving planes with penalty, damping and Coulomb
+        friction. Captured step graphs are dropped and an enabled history restarts; the loads stay
+        in force. A refused call leaves the previous walls in force."""
+        s, keep = walls.c()
+        check(self.L.hakai_set_walls(self.ctx, ctypes.byref(s)))
+        del keep
+
+    def clear_walls(self):
+        check(self.L.hakai_clear_walls(self.ctx))
+
+    def wall_force(self, t: float, d_time: float | None = None) -> np.ndarray:
+        """The wall force of step t at the current device state, without contact and loads (3nN; no step)."""
+        f = np.zeros(3 * self.model.nNode)
+        check(self.L.hakai_wall_force(self.ctx, float(t), float(self.model.dt if d_time is None else d_time), ptr(f)))
         return f
 
     # -- profiling (HIP events on the context's own stream) ------------------------------------

@@ -173,6 +173,10 @@ struct Owned {
     std::vector<int32_t> ld_amp_n, ld_cl_amp, ld_g_amp, ld_pr_face, ld_pr_amp;
     std::vector<int64_t> ld_amp_off, ld_cl_dof, ld_pr_elem;
     std::vector<double> ld_amp_t, ld_amp_v, ld_cl_val, ld_g_acc, ld_pr_val;
+    // rigid walls (*Rigid Wall), what pub.walls points to
+    std::vector<int32_t> wl_amp_n, wl_amp;
+    std::vector<int64_t> wl_amp_off, wl_node_off, wl_nodes;
+    std::vector<double> wl_amp_t, wl_amp_v, wl_origin, wl_normal, wl_motion, wl_stiff, wl_scale, wl_damp, wl_fric;
 };
 
 void read_lines(const char* path, std::vector<std::string>& lines) {
@@ -764,6 +768,79 @@ void parse(const char* path, Owned& o) {
     for (long long el : o.ld_pr_elem)
         if (el < 1 || el > nElement) throw ParseError{"load: element out of range"};
 
+    // ---- rigid walls: *Rigid Wall, name=.. [, nset=..] [, amplitude=..] [, stiffness=..] [, scale=..]
+    // [, damping=..] [, friction=..], then one data line ox, oy, oz, nx, ny, nz [, mx, my, mz]. A HAKAI
+    // keyword (the reference's reader skips it); an unknown parameter, node set or amplitude, a
+    // malformed data line or a wall too many is an error, never a silent skip.
+    o.wl_node_off.push_back(0);
+    for (long long li = 1; li <= n; ++li) {
+        if (!has(line(li), "*Rigid Wall")) continue;
+        if (o.wl_amp.size() >= (size_t)HAKAI_MAX_WALLS) throw ParseError{"*Rigid Wall: more than 32 walls"};
+        double stiff = 0.0, scale = 0.5, damp = 0.0, fric = 0.0;
+        int32_t amp = -1;
+        std::string wname;
+        const auto head = split(nospace(line(li)), ',', false);
+        for (size_t k = 1; k < head.size(); ++k) {
+            const std::string& tok = head[k];
+            if (tok.rfind("name=", 0) == 0) {
+                wname = after(tok, "name=");
+            } else if (tok.rfind("nset=", 0) == 0) {
+                const std::string set = after(tok, "nset=");
+                const std::vector<long long> nodes = nodes_of(set, true);
+                if (nodes.empty()) throw ParseError{"*Rigid Wall: unknown node set " + set};
+                for (long long q : nodes) {
+                    if (q < 1 || q > nNode) throw ParseError{"*Rigid Wall: node out of range in " + set};
+                    o.wl_nodes.push_back(q);
+                }
+            } else if (tok.rfind("amplitude=", 0) == 0) {
+                const std::string name = after(tok, "amplitude=");
+                const Amp* hit = nullptr;
+                for (auto& a : AMP)
+                    if (a.name == name) {
+                        hit = &a;
+                        break;
+                    }
+                if (!hit) throw ParseError{"*Rigid Wall: unknown amplitude " + name};
+                o.wl_amp_n.push_back((int32_t)hit->time.size());
+                o.wl_amp_off.push_back((int64_t)o.wl_amp_t.size());
+                o.wl_amp_t.insert(o.wl_amp_t.end(), hit->time.begin(), hit->time.end());
+                o.wl_amp_v.insert(o.wl_amp_v.end(), hit->value.begin(), hit->value.end());
+                amp = (int32_t)o.wl_amp_n.size() - 1;
+            } else if (tok.rfind("stiffness=", 0) == 0) {
+                stiff = parse_f(after(tok, "stiffness="));
+            } else if (tok.rfind("scale=", 0) == 0) {
+                scale = parse_f(after(tok, "scale="));
+            } else if (tok.rfind("damping=", 0) == 0) {
+                damp = parse_f(after(tok, "damping="));
+            } else if (tok.rfind("friction=", 0) == 0) {
+                fric = parse_f(after(tok, "friction="));
+            } else {
+                throw ParseError{"*Rigid Wall: unknown parameter " + tok};
+            }
+        }
+        if (wname.empty()) throw ParseError{"*Rigid Wall: name= is required"};
+        int rows = 0;
+        for (long long i = li + 1; i <= n; ++i) {
+            if (has(line(i), "*")) break;
+            const auto t = split(nospace(line(i)), ',', true);
+            if (t.size() == 1 && t[0].empty()) continue;
+            if (rows++ || (t.size() != 6 && t.size() != 9))
+                throw ParseError{"*Rigid Wall: expected one line 'ox, oy, oz, nx, ny, nz [, mx, my, mz]': " + line(i)};
+            for (int c = 0; c < 3; ++c) {
+                o.wl_origin.push_back(parse_f(t[c]));
+                o.wl_normal.push_back(parse_f(t[3 + c]));
+                o.wl_motion.push_back(t.size() == 9 ? parse_f(t[6 + c]) : 0.0);
+            }
+        }
+        if (rows != 1) throw ParseError{"*Rigid Wall: " + wname + " has no data line"};
+        o.wl_amp.push_back(amp);
+        o.wl_stiff.push_back(stiff);
+        o.wl_scale.push_back(scale);
+        o.wl_damp.push_back(damp);
+        o.wl_fric.push_back(fric);
+        o.wl_node_off.push_back((int64_t)o.wl_nodes.size());
+    }
+
     // ---- flatten into the C view
     o.coord = coordmat;
     o.elem.assign(elementmat.begin(), elementmat.end());
@@ -864,6 +941,22 @@ void parse(const char* path, Owned& o) {
     p.loads.press_face = o.ld_pr_face.data();
     p.loads.press_value = o.ld_pr_val.data();
     p.loads.press_amp = o.ld_pr_amp.data();
+    p.walls.n_amp = (int32_t)o.wl_amp_n.size();
+    p.walls.amp_n = o.wl_amp_n.data();
+    p.walls.amp_off = o.wl_amp_off.data();
+    p.walls.amp_time = o.wl_amp_t.data();
+    p.walls.amp_value = o.wl_amp_v.data();
+    p.walls.n_wall = (int32_t)o.wl_amp.size();
+    p.walls.origin = o.wl_origin.data();
+    p.walls.normal = o.wl_normal.data();
+    p.walls.motion = o.wl_motion.data();
+    p.walls.amp = o.wl_amp.data();
+    p.walls.stiffness = o.wl_stiff.data();
+    p.walls.scale = o.wl_scale.data();
+    p.walls.damping = o.wl_damp.data();
+    p.walls.friction = o.wl_fric.data();
+    p.walls.node_off = o.wl_node_off.data();
+    p.walls.nodes = o.wl_nodes.data();
 }
 
 void pusai_table(double P[8][3][8]) {  // cal_Pusai_hexa, v2/HAKAI_j.jl:1895-1943
@@ -990,6 +1083,7 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
         return r;
     if ((M->loads.n_cload > 0 || M->loads.n_grav > 0 || M->loads.n_press > 0) && (r = hakai_set_loads(c, &M->loads)))
         return r;
+    if (M->walls.n_wall > 0 && (r = hakai_set_walls(c, &M->walls))) return r;
     if ((r = hakai_reset_state(c, M->n_ic_dofs, M->ic_dofs, M->ic_values, d_time))) return r;
     const long long n_steps = time_num >= 1.0 ? (long long)std::floor(time_num) : 0;
     const long long d_out = (long long)std::floor(time_num / 100);  // output_num = 100 (:471-472)

@@ -218,8 +218,9 @@ int hakai_set_tuning(hakai_ctx* ctx, const char* key, int64_t value);
  * force assembled from u_k (what step k+1's nodal update consumes), du_k = u_k - u_{k-1},
  * c_k = (du_{k+1} + du_k) / 2. Step t = k+1 sums, per set:
  *    0-2  F_int[c]  Q_k (the reaction force on a clamped set)
- *    3-5  F_ext[c]  f_k (0 without contact and loads; with hakai_set_loads the step's total external
- *                   force, contact plus loads, so W_ext is their work and the identity below holds)
+ *    3-5  F_ext[c]  f_k (0 without contact, loads and walls; with hakai_set_loads / hakai_set_walls the
+ *                   step's total external force, contact plus loads plus walls, so W_ext is their
+ *                   work and the identity below holds)
  *    6-8  P[c]      m du_{k+1} / dt
  *    9    KE        1/2 m sum_c (du_{k+1} / dt)^2 (the velocity a download after this step reports)
  *   10    W_int     accumulated since the (re)start: += sum_c Q_k c_k
@@ -308,7 +309,8 @@ int hakai_history_combine(int32_t n_ranks, int32_t n_total, int64_t n, const int
  *            eigenvalue of the element's ELASTIC B-bar stiffness, so the minimum over the elements is
  *            a guaranteed lower bound of the linear critical step 2 / omega_max when diag_M is the
  *            lumped mass times mass_scaling (what every driver uploads). The plastic tangent is no
- *            stiffer; the PENALTY STIFFNESS OF CONTACT IS NOT COVERED. (DESIGN.md section 2,
+ *            stiffer; the PENALTY STIFFNESS OF CONTACT AND OF RIGID WALLS (hakai_set_walls) IS NOT
+ *            COVERED. (DESIGN.md section 2,
  *            "Stable time step", has the derivation.)
  * An active element with V0 <= 0, V == 0 or A_max == 0 reports 0 for both; a deleted element reports
  * +inf and counts nowhere. The sums over the Gauss points are one fixed pairwise tree and the
@@ -343,7 +345,8 @@ int hakai_stable_dt_write_csv(const char* path, int64_t n, const int64_t* steps,
  *   + the node's pressure contributions, in ascending order of the press_* index.
  * That total is what the nodal update, the multi-GPU interface fix and the history output take as
  * the external force (history's F_ext / W_ext are then contact plus loads). A node without any load
- * gets the contact force (or zero) unchanged. Without loads nothing is launched or allocated.
+ * gets the contact force (or zero) unchanged. Without loads (and without rigid walls, hakai_set_walls
+ * below, whose forces join this sum after the pressure contributions) nothing is launched or allocated.
  *
  * Amplitude tables: n_amp tables, table a holds amp_n[a] >= 2 rows (time, value) at amp_off[a]. A
  * load names a table by index; -1 is the constant 1. The value at ct = t * d_time (in a captured
@@ -398,6 +401,88 @@ typedef struct {
 int hakai_set_loads(hakai_ctx* ctx, const hakai_loads_t* loads);
 int hakai_clear_loads(hakai_ctx* ctx);
 int hakai_load_force(hakai_ctx* ctx, double t, double d_time, double* load_force);
+
+/* ---- rigid walls: moving planes with penalty, damping and Coulomb friction -------------------- */
+/* The reference has no rigid wall (its decks mesh a second body): the definition is this text. Up to
+ * HAKAI_MAX_WALLS infinite planes. Wall w has
+ *   origin[3], normal[3]  any finite non-zero normal; the host normalises it once,
+ *                         n = normal / sqrt((nx*nx + ny*ny) + nz*nz), each component divided (a
+ *                         length that is not finite and positive is refused). n points into the
+ *                         half-space the nodes may occupy;
+ *   motion[3], amp        the wall is rigid and displaced by motion * amp(tau); amp is an index into the
+ *                         walls' own amplitude tables (layout and rule of hakai_loads_t's), -1 the
+ *                         constant 1;
+ *   stiffness >= 0 (force per length), scale >= 0: node i sees the penalty
+ *                         k_i = stiffness + scale * (m_i / (dt * dt)), m_i the uploaded diag_M entry of
+ *                         the node's first dof, so a mass-scaled model keeps its penalty ratio. An
+ *                         isolated node on that spring alone is stable for scale < 4; the element
+ *                         stiffness at the node shares that budget (and hakai_stable_dt's dt_safe does
+ *                         not cover the wall): the choice is the caller's;
+ *   damping >= 0 (zeta, fraction of critical), friction >= 0 (mu);
+ *   nodes                 node_off[w] .. node_off[w+1] into nodes (1-based; local ids on a rank); an
+ *                         empty range means every node; a node listed twice counts once.
+ * Step t evaluates the force on the configuration its nodal update reads, u_k = disp, whose time is
+ * tau0 = (t - 1.0) * d_time; with taum = (t - 2.0) * d_time, s0 = amp(tau0), sm = amp(taum) (in a captured
+ * graph tau0 = (*t_rd) * dt and taum = (*t_rd - 1.0) * dt from the device step counter: the same bits),
+ * u_km = disp_pre, m = m_i, dt = d_time, per component c and every operation rounded once:
+ *     o[c]  = origin[c] + motion[c] * s0
+ *     vw[c] = motion[c] * ((s0 - sm) / dt)
+ *     x[c]  = coord[c] + u_k[c]
+ *     v[c]  = (u_k[c] - u_km[c]) / dt - vw[c]
+ *     g     = ((x[0] - o[0]) * n[0] + (x[1] - o[1]) * n[1]) + (x[2] - o[2]) * n[2]
+ *     d     = -g
+ * The wall acts only if d > 0 (strict: a node exactly on the plane gets nothing). Then
+ *     k     = stiffness + scale * (m / (dt * dt))
+ *     vn    = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2]
+ *     cd    = (2.0 * zeta) * sqrt(m * k)
+ *     N     = max(k * d - cd * vn, 0.0)                       non-adhesive
+ *     vt[c] = v[c] - vn * n[c]
+ *     s     = sqrt((vt[0] * vt[0] + vt[1] * vt[1]) + vt[2] * vt[2])
+ *     T     = min(mu * N, (m * s) / dt)                       the force that stops the slip in one step
+ *     F[c]  = s > 0 ? N * n[c] - (T / s) * vt[c] : N * n[c]
+ * csrc/hakai_walls_node.hpp is the one definition of this operation order, for the device and the host.
+ * Place in the node's sum (hakai_set_loads above): after the pressure contributions, walls in
+ * ascending index, each F added componentwise with one rounding per addition:
+ *     contact (+0.0) + concentrated + gravity + pressure + walls,
+ * formed in the same single launch as the loads; independent of grid, launch form and rank. The total
+ * is what the nodal update, the interface fix and the history output take (history's F_ext / W_ext
+ * carry the wall; the set-0 identity holds). Without walls and loads nothing is launched or allocated.
+ *
+ * hakai_set_walls replaces the walls (the arrays are copied); n_wall == 0 clears them. HAKAI_ERR_ARG
+ * changes nothing and leaves the previous walls in force: more than HAKAI_MAX_WALLS walls or a
+ * negative count, a node out of range, a zero or non-finite normal, a non-finite origin or motion,
+ * a non-finite or negative stiffness, scale, damping or friction, an amplitude index out of range, a
+ * table with fewer than two rows or a non-finite row. HAKAI_ERR_STATE: before hakai_upload_model.
+ * A context with a communicator accepts walls: every rank lists each of its local nodes, shared ones
+ * included, with local ids, and the result is bit-identical to one context.
+ * hakai_upload_model clears the walls; hakai_set_bc, hakai_reset_state and hakai_upload_state keep
+ * them. Loads and walls are independent: setting or clearing one leaves the other in force.
+ * hakai_set_walls and hakai_clear_walls drop captured step graphs and, with history enabled, restart
+ * the history. hakai_wall_force is a probe like hakai_load_force: the wall force alone (3nN, without
+ * contact and loads) of step t at the current state, no step; zeros without walls. hakai_load_force
+ * keeps returning the loads only, hakai_contact_force the contact only. */
+#define HAKAI_MAX_WALLS 32
+typedef struct {
+    int32_t n_amp;
+    const int32_t* amp_n;       /* [n_amp] rows per table (>= 2) */
+    const int64_t* amp_off;     /* [n_amp] into amp_time / amp_value */
+    const double* amp_time;
+    const double* amp_value;
+    int32_t n_wall;
+    const double* origin;       /* [3 n_wall] */
+    const double* normal;       /* [3 n_wall] */
+    const double* motion;       /* [3 n_wall] */
+    const int32_t* amp;         /* [n_wall] table index, -1: constant 1 */
+    const double* stiffness;    /* [n_wall] */
+    const double* scale;        /* [n_wall] */
+    const double* damping;      /* [n_wall] */
+    const double* friction;     /* [n_wall] */
+    const int64_t* node_off;    /* [n_wall + 1] into nodes */
+    const int64_t* nodes;       /* 1-based node ids; an empty range: every node */
+} hakai_walls_t;
+int hakai_set_walls(hakai_ctx* ctx, const hakai_walls_t* walls);
+int hakai_clear_walls(hakai_ctx* ctx);
+int hakai_wall_force(hakai_ctx* ctx, double t, double d_time, double* wall_force);
 
 /* ---- contact: all-exterior instance-vs-instance penalty contact --------- */
 /* Enables contact for the uploaded model: contact_flag as readInpFile sets it (1 = *Contact,
@@ -509,6 +594,13 @@ typedef struct {
      * without these keywords has every count 0. An unknown load type, surface, set or amplitude is a
      * parse error. */
     hakai_loads_t loads;
+    /* *Rigid Wall, name=NAME [, nset=NAME] [, amplitude=NAME] [, stiffness=K] [, scale=S] [, damping=Z]
+     * [, friction=MU], then one data line ox, oy, oz, nx, ny, nz [, mx, my, mz]: a HAKAI keyword (the
+     * reference's reader skips keywords it does not know). Defaults: stiffness 0, scale 0.5, damping 0,
+     * friction 0, no motion, every node; nset gives global ids. An unknown parameter, node set or
+     * amplitude, a malformed or missing data line and a 33rd wall are parse errors. A deck without
+     * the keyword has n_wall 0. */
+    hakai_walls_t walls;
 } hakai_inp_model_t;
 
 int hakai_inp_read(const char* path, hakai_inp_model_t** out);
@@ -566,7 +658,8 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
  * out_dir/stable_dt.csv (hakai_stable_dt_write_csv) at the end; verbose: one stderr line the first
  * time d_time > dt_est and one the first time d_time > dt_safe, each naming the element. The VTK
  * files and stdout are the same bytes with and without; unset, nothing changes.
- * The deck's loads (hakai_inp_model_t::loads) are applied with hakai_set_loads. */
+ * The deck's loads (hakai_inp_model_t::loads) are applied with hakai_set_loads, its rigid walls
+ * (hakai_inp_model_t::walls) with hakai_set_walls. */
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose);
 /* The sets of that history output, for another driver of the same deck (the N-GPU driver, hakai.run):
  * n_sets (without set 0), set_off[n_sets+1] (room for 16) into set_nodes (global 1-based ids;

@@ -306,6 +306,14 @@ load_force!(c::Ctx, load_force, t, d_time) =
     check(ccall((:hakai_load_force, lib), Cint, (Ptr{Cvoid}, Float64, Float64, Ptr{Float64}),
                 c.p, t, d_time, load_force))
 clear_loads(c::Ctx) = check(ccall((:hakai_clear_loads, lib), Cint, (Ptr{Cvoid},), c.p))
+# Rigid walls (include/hakai_hip.h, "rigid walls"): wall_force! is the probe of the wall force alone
+# (step t at the current state, without contact and loads), clear_walls drops them. Walls are set from
+# a deck's *Rigid Wall by hakai_run_inp; hakai_set_walls takes a hakai_walls_t of flat arrays, which
+# this shim does not mirror yet.
+wall_force!(c::Ctx, wall_force, t, d_time) =
+    check(ccall((:hakai_wall_force, lib), Cint, (Ptr{Cvoid}, Float64, Float64, Ptr{Float64}),
+                c.p, t, d_time, wall_force))
+clear_walls(c::Ctx) = check(ccall((:hakai_clear_walls, lib), Cint, (Ptr{Cvoid},), c.p))
 function contact_stats(c::Ctx)
     st = zeros(Int64, 10)
     check(ccall((:hakai_contact_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int32), c.p, st, length(st)))
