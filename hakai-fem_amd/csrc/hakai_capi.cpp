@@ -3,6 +3,15 @@
 // Owns the persistent device context: model, Gauss-point state in SoA, ping-pong displacement
 // buffers, the node->element incidence CSR used for the deterministic force gather, BC tables,
 // deletion log and per-kernel HIP-event timers. One HIP stream per context.
+//
+// Where the code is: this file has the context's creation and destruction, the model, BC and state
+// uploads and downloads, profiling, the tuning and stat keys (owner keys: hakai_own.cpp, contact
+// keys: hakai_contact.hip), the deletion log, negative Jacobians, node averages, the stateless
+// drop-ins and the kernel-argument builders. hakai_step.cpp is the step driver (one step, graph
+// capture and replay, the overflow rollback, hakai_step and hakai_step_group); hakai_step_view.hpp
+// the host's view of the stepping state, whose member functions alone change it; hakai_own.cpp the
+// run time of owner-computed assembly (hkc::Own); hakai_devmem.hpp the HIP error check and the
+// device buffers every translation unit uses.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,7 +29,6 @@
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
 #include "hakai_loads.hpp"
-#include "hakai_own_plan.hpp"
 #include "hakai_stable_dt.hpp"
 
 using hk::DevMat;
@@ -47,44 +55,13 @@ int hip_fail(hipError_t e, const char* what) {
 
 }  // namespace hkc
 
+using hkc::dalloc;
+using hkc::dfree;
 using hkc::fail;
 using hkc::hip_fail;
-
-#define HIPCHK(x)                                           \
-    do {                                                    \
-        hipError_t _e = (x);                                \
-        if (_e != hipSuccess) return hip_fail(_e, #x);      \
-    } while (0)
-
-template <class T>
-static hipError_t dalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc((void**)p, n * sizeof(T));
-}
-
-template <class T>
-static void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
+using hkc::QSrc;
 
 namespace hkc {
-
-static void own_free(hakai_ctx* c) {
-    dfree(c->d_own_off);
-    dfree(c->d_own_seq);
-    dfree(c->d_own_bstart);
-    dfree(c->d_own_list);
-    dfree(c->d_own_q);
-    dfree(c->d_own_rp);
-    dfree(c->d_own_rows);
-    dfree(c->d_own_ridx);
-    dfree(c->d_own_dump);
-    c->own_built_g = -1;
-    c->own_for_g0 = -1;
-    c->own_valid = false;
-}
 
 static void free_model(hakai_ctx* c) {
     contact_destroy(c);
@@ -241,29 +218,18 @@ void prof_end(hakai_ctx* c, EventPair* p) {
     (void)hipEventRecord(p->b, c->stream);
     c->ev_pending.push_back(*p);
 }
-void graph_invalidate(hakai_ctx* c) {
-    c->epoch++;
-    c->tdev_next = -1;
-}
-static void graph_free(hakai_ctx* c) {
-    for (int g = 0; g < 2; ++g)
-        for (int p = 0; p < 2; ++p)
-            if (c->g_exec[g][p]) {
-                (void)hipGraphExecDestroy(c->g_exec[g][p]);
-                c->g_exec[g][p] = nullptr;
-                c->g_epoch[g][p] = -1;
-            }
-}
 }  // namespace hkc
 
 
-// Kernel arguments of the element update for the context's current buffers.
-static hk::ElemArgs elem_args(hakai_ctx* c) {
+namespace hkc {
+
+// Kernel arguments of the element update with disp = d_u[cur].
+hk::ElemArgs elem_args(const hakai_ctx* c, int cur) {
     hk::ElemArgs ea;
     std::memset(&ea, 0, sizeof ea);
     ea.coord = c->d_coord;
-    ea.u = c->d_u[c->cur];
-    ea.u_pre = c->d_u[1 - c->cur];
+    ea.u = c->d_u[cur];
+    ea.u_pre = c->d_u[1 - cur];
     ea.conn = c->d_conn;
     ea.flag = c->d_flag;
     ea.mat = c->d_mat;
@@ -285,8 +251,8 @@ static hk::ElemArgs elem_args(hakai_ctx* c) {
     ea.del_step = c->d_del_step;
     ea.step_i = 0;
     ea.any_plastic = c->any_plastic ? 1 : 0;
-    // nEp / 32 = batches of 32 elements (kEPB); small meshes take the one-batch-per-block kernel
-    ea.pipe_blocks = (c->nEp / 32 >= (long long)c->pipe_min * c->pipe_blocks) ? c->pipe_blocks : 0;
+    // small meshes take the one-batch-per-block kernel
+    ea.pipe_blocks = pipe_grid(c) > 0 ? c->pipe_blocks : 0;
     ea.gp_nt = c->gp_nt;
     ea.nmat = c->nmat;
     ea.exact = c->elem_exact;
@@ -294,6 +260,52 @@ static hk::ElemArgs elem_args(hakai_ctx* c) {
     ea.poison = c->d_poison;
     return ea;
 }
+
+// Kernel arguments of the nodal update: Q from the uploaded-Q buffer, the previous element step's
+// owner-computed sums, or the fe gather (sv.q); the caller adds the external force and fused BCs.
+hk::NodalArgs nodal_args(const hakai_ctx* c, double d_time) {
+    hk::NodalArgs na;
+    na.u = c->d_u[c->sv.cur];
+    na.u_pre_out = c->d_u[1 - c->sv.cur];
+    na.mass = c->d_mass;
+    na.inc_ptr = c->d_inc_ptr;
+    na.inc = c->d_inc;
+    na.inc8 = c->d_inc8;
+    na.fe = c->d_fe;
+    na.qbuf = c->sv.q == QSrc::Buf ? c->d_qbuf : nullptr;
+    na.fext = nullptr;
+    na.nN = c->nN;
+    na.dt = d_time;
+    na.bc_of_node = nullptr;
+    const OwnSums o = c->sv.q == QSrc::Own ? own_sums(c) : OwnSums{nullptr, nullptr, nullptr, nullptr};
+    na.own_q = o.q;
+    na.own_rp = o.rp;
+    na.own_rows = o.rows;
+    na.own_ridx = o.ridx;
+    na.poison = c->d_poison;
+    return na;
+}
+
+// Kernel arguments of the boundary conditions of step t, written into disp_new.
+hk::BCArgs bc_args(const hakai_ctx* c, double t, double d_time) {
+    hk::BCArgs ba;
+    ba.dof = c->d_bc_dof;
+    ba.grp = c->d_bc_grp;
+    ba.val = c->d_bc_val;
+    ba.n = c->nbc;
+    ba.amp_n = c->d_amp_n;
+    ba.amp_off = c->d_amp_off;
+    ba.amp_t = c->d_amp_t;
+    ba.amp_v = c->d_amp_v;
+    ba.out = c->d_u[1 - c->sv.cur];
+    ba.ct = t * d_time;
+    ba.t_rd = c->gr.trd;
+    ba.dt = d_time;
+    ba.poison = c->d_poison;
+    return ba;
+}
+
+}  // namespace hkc
 
 // Element forces [nEp][8][3] <-> the reference's Qe (24 x nE): the same layout.
 static int fe_download_qe(hakai_ctx* c, double* Qe) {
@@ -395,7 +407,7 @@ int hakai_create(hakai_ctx** out, int device) {
         }
     }
     if (const char* v = std::getenv("HAKAI_ELEM_EXACT")) c->elem_exact = std::atoi(v) ? 1 : 0;
-    if (const char* v = std::getenv("HAKAI_OWN_ASSEMBLY")) c->own_assembly = std::atoi(v) ? 1 : 0;
+    if (const char* v = std::getenv("HAKAI_OWN_ASSEMBLY")) c->own.assembly = std::atoi(v) ? 1 : 0;
     *out = c;
     return 0;
 }
@@ -620,13 +632,12 @@ int hakai_set_bc(hakai_ctx* c, const hakai_bc_t* bc) {
 
 int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const double* ic_values, double d_time) {
     if (c) hkc::graph_invalidate(c);  // captured steps may hold stale buffers or settings
-    if (c) c->own_valid = false;  // the next nodal update gathers fe (or the uploaded Q)
     if (!c) return fail(HAKAI_ERR_ARG, "null");
     if (!c->model_ok) return fail(HAKAI_ERR_STATE, "reset_state before upload_model");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t fn = 3 * (size_t)c->nN;
-    c->cur = 0;
+    c->sv.restart(false);  // the next nodal update gathers the zeroed fe
     HIPCHK(hipMemsetAsync(c->d_u[0], 0, fn * sizeof(double), s));
     HIPCHK(hipMemsetAsync(c->d_u[1], 0, fn * sizeof(double), s));
     HIPCHK(hipMemsetAsync(c->d_fe, 0, (size_t)c->fe_len * sizeof(double), s));
@@ -634,9 +645,6 @@ int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const 
     HIPCHK(hk::launch_reset_gp(c->d_stress, c->d_strain, c->d_eqps, c->d_yield, c->d_triax, c->d_flag, c->d_mat,
                                c->d_mats, c->nE, c->nEp, c->ld, s));
     c->h_velo0.assign(fn, 0.0);
-    c->q_from_buf = false;
-    c->fe_ok = c->triax_ok = true;
-    c->steps_done = 0;
     HIPCHK(hipMemsetAsync(c->d_poison, 0, 2 * sizeof(int), s));
     hkc::comm_reset(c);
     if (n_ic > 0) {
@@ -648,7 +656,7 @@ int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const 
             dpre[d - 1] = -ic_values[j] * d_time;
             c->h_velo0[d - 1] = ic_values[j];
         }
-        HIPCHK(hipMemcpyAsync(c->d_u[1 - c->cur], dpre.data(), fn * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_u[1 - c->sv.cur], dpre.data(), fn * sizeof(double), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     c->state_ok = true;
@@ -657,8 +665,6 @@ int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const 
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
-
-static int own_materialize(hakai_ctx* c);
 
 int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
     if (c) hkc::graph_invalidate(c);  // captured steps may hold stale buffers or settings
@@ -669,25 +675,25 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
     // steps a contact overflow skipped, owner-computed assembly left the last element step's forces
     // only as node sums (fe is an earlier step's): they become the uploaded Q, the same bits, and an
     // upload that also deletes elements (whose fe rows it would zero) must bring Q or Qe itself.
-    if (c->own_valid && !c->fe_ok && !st->Q && !st->Qe) {
+    if (c->sv.q == QSrc::Own && !c->sv.fe_ok && !st->Q && !st->Qe) {
         bool dels = false;
         for (long long e = 0; st->element_flag && e < c->nE && !dels; ++e) dels = st->element_flag[e] == 0;
         if (dels || c->comm)
             return fail(HAKAI_ERR_STATE, "upload_state: the last element step's forces exist only as owner-computed "
                         "node sums (a contact overflow skipped the call's last step); upload Q (from "
                         "hakai_download_state) or Qe with this state");
-        if (int r = own_materialize(c)) return r;
+        if (int r = hkc::own_materialize(c)) return r;
     }
-    c->own_valid = false;
+    c->sv.restart(true);
     hipStream_t s = c->stream;
     const size_t fn = 3 * (size_t)c->nN, nGP = 8 * (size_t)c->nE;
-    if (st->disp) HIPCHK(hipMemcpyAsync(c->d_u[c->cur], st->disp, fn * sizeof(double), hipMemcpyHostToDevice, s));
+    if (st->disp) HIPCHK(hipMemcpyAsync(c->d_u[c->sv.cur], st->disp, fn * sizeof(double), hipMemcpyHostToDevice, s));
     if (st->disp_pre)
-        HIPCHK(hipMemcpyAsync(c->d_u[1 - c->cur], st->disp_pre, fn * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_u[1 - c->sv.cur], st->disp_pre, fn * sizeof(double), hipMemcpyHostToDevice, s));
     if (st->velo) c->h_velo0.assign(st->velo, st->velo + fn);
     if (st->Q) {
         HIPCHK(hipMemcpyAsync(c->d_qbuf, st->Q, fn * sizeof(double), hipMemcpyHostToDevice, s));
-        c->q_from_buf = true;
+        c->sv.q_uploaded();
     }
     if (st->integ_stress || st->integ_strain) {
         double* tmp = nullptr;
@@ -738,8 +744,6 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
     }
     HIPCHK(hipMemsetAsync(c->d_poison, 0, 2 * sizeof(int), s));
     HIPCHK(hipStreamSynchronize(s));
-    c->steps_done = 0;
-    c->fe_ok = c->triax_ok = true;
     hkc::comm_reset(c);
     c->state_ok = true;
     if (int r = hkc::history_restart(c)) return r;
@@ -753,26 +757,26 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
 int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
     if (!c || !st) return fail(HAKAI_ERR_ARG, "null");
     if (!c->state_ok) return fail(HAKAI_ERR_STATE, "download_state without state");
-    if (st->Qe && !c->fe_ok)
+    if (st->Qe && !c->sv.fe_ok)
         return fail(HAKAI_ERR_STATE, "download_state: Qe is not available after a call whose last steps a contact "
                     "overflow skipped (owner-computed assembly keeps node sums only); Q is -- or step once more");
-    if (st->integ_triax_stress && !c->triax_ok)
+    if (st->integ_triax_stress && !c->sv.triax_ok)
         return fail(HAKAI_ERR_STATE, "download_state: integ_triax_stress is not available after a call whose last "
                     "steps a contact overflow skipped (it is stored on a call's last step); step once more");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t fn = 3 * (size_t)c->nN, nGP = 8 * (size_t)c->nE;
     HIPCHK(hipStreamSynchronize(s));
-    if (st->disp) HIPCHK(hipMemcpyAsync(st->disp, c->d_u[c->cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (st->disp) HIPCHK(hipMemcpyAsync(st->disp, c->d_u[c->sv.cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
     if (st->disp_pre)
-        HIPCHK(hipMemcpyAsync(st->disp_pre, c->d_u[1 - c->cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(st->disp_pre, c->d_u[1 - c->sv.cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
     if (st->velo) {
-        if (c->steps_done == 0) {
+        if (c->sv.steps_done == 0) {
             std::memcpy(st->velo, c->h_velo0.data(), fn * sizeof(double));
         } else {  // velo = d_disp / d_time with d_disp = disp_new - disp (v2/HAKAI_j.jl:625-628)
             std::vector<double> a(fn), b(fn);
-            HIPCHK(hipMemcpyAsync(a.data(), c->d_u[c->cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(b.data(), c->d_u[1 - c->cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(a.data(), c->d_u[c->sv.cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(b.data(), c->d_u[1 - c->sv.cur], fn * sizeof(double), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             for (size_t i = 0; i < fn; ++i) {
                 const double dd = a[i] - b[i];
@@ -781,14 +785,15 @@ int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
         }
     }
     if (st->Q) {
-        if (c->q_from_buf) {
+        if (c->sv.q == QSrc::Buf) {
             HIPCHK(hipMemcpyAsync(st->Q, c->d_qbuf, fn * sizeof(double), hipMemcpyDeviceToHost, s));
         } else {
             double* tmp = nullptr;
             HIPCHK(dalloc(&tmp, fn));
-            if (c->own_valid)  // the last element step's owner-computed sums (fe may be stale)
-                HIPCHK(hk::launch_own_q(c->d_own_q, c->d_own_rp, c->d_own_ridx, c->d_own_rows, tmp, c->nN, s));
-            else
+            if (c->sv.q == QSrc::Own) {  // the last element step's owner-computed sums (fe may be stale)
+                const hkc::OwnSums o = hkc::own_sums(c);
+                HIPCHK(hk::launch_own_q(o.q, o.rp, o.ridx, o.rows, tmp, c->nN, s));
+            } else
                 HIPCHK(hk::launch_gather_q(c->d_inc_ptr, c->d_inc, c->d_fe, tmp, c->nN, s));
             HIPCHK(hipMemcpyAsync(st->Q, tmp, fn * sizeof(double), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
@@ -830,491 +835,11 @@ int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Owner-computed assembly (tuning "own_assembly"): the planner is hakai_own_plan.cpp, the entry
-// format hakai_own_entry.hpp; here the plan is uploaded and switched on and off.
-// ---------------------------------------------------------------------------------------------
-static bool own_upload(hakai_ctx* c, const hk::OwnSched& sc, const hk::OwnPlan& pl) {
-    hkc::own_free(c);
-    const long long nN = c->nN, G = (long long)sc.bstart.size() - 1;
-    std::vector<int> bst(sc.bstart.begin(), sc.bstart.end());
-    hipStream_t s = c->stream;
-    auto up = [&](int** d, const std::vector<int>& h) -> hipError_t {
-        hipError_t e = dalloc(d, std::max<size_t>(h.size(), 1));
-        if (e == hipSuccess && !h.empty()) e = hipMemcpyAsync(*d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s);
-        return e;
-    };
-    if (up(&c->d_own_off, pl.off) || up(&c->d_own_seq, sc.seq) || up(&c->d_own_bstart, bst) ||
-        up(&c->d_own_list, pl.list) || up(&c->d_own_rp, pl.rp) || up(&c->d_own_ridx, pl.ridx) ||
-        dalloc(&c->d_own_q, 3 * (size_t)nN) || dalloc(&c->d_own_rows, 3 * (size_t)std::max(pl.rows, 1LL)) ||
-        dalloc(&c->d_own_dump, 8 * (size_t)G) ||
-        hipMemsetAsync(c->d_own_q, 0, 3 * (size_t)nN * sizeof(double), s) ||  // nodes without elements
-        hipStreamSynchronize(s)) {
-        hkc::own_free(c);
-        return false;
-    }
-    c->own_nop = (int)pl.ne;
-    c->own_slots = pl.max_slots;
-    c->own_rows = pl.rows;
-    c->own_entries = pl.ne;
-    c->own_built_g = G;
-    c->own_s = pl.S;
-    c->own_round2 = pl.round2;
-    c->own_banded = sc.banded ? 1 : 0;
-    return true;
-}
-
-// Grid of the persistent kernel for this context (0: the one-batch kernel runs).
-static long long own_grid(const hakai_ctx* c) {
-    const long long nb = c->nEp / 32;
-    const bool pipe = nb >= (long long)c->pipe_min * c->pipe_blocks && c->pipe_blocks > 0;
-    return pipe ? std::min<long long>(nb, c->pipe_blocks) : 0;
-}
-
-// This step's element update uses owner-computed assembly (builds the lists on first use). The
-// grid is the persistent kernel's, or 8x that (blocks then run in waves) when the default ranges
-// span so much of a wide cross-section that too many sums stay open in a block.
-// Owner assembly stops being used while the previous element step's forces exist only as its
-// node sums (a tuning change, a list rebuild): hand the next nodal update Q through the uploaded-Q
-// buffer, the same bits (k_own_q = k_nodal's own additions). Multi-GPU ranks cannot: their next
-// interface fix needs the per-contribution rows.
-static int own_materialize(hakai_ctx* c) {
-    if (!c->own_valid) return 0;
-    if (c->comm)
-        return fail(HAKAI_ERR_STATE, "owner-computed assembly cannot be switched off or rebuilt on a multi-GPU rank "
-                    "mid-run: upload or reset the state first");
-    HIPCHK(hk::launch_own_q(c->d_own_q, c->d_own_rp, c->d_own_ridx, c->d_own_rows, c->d_qbuf, c->nN, c->stream));
-    c->q_from_buf = true;
-    c->own_valid = false;
-    return 0;
-}
-
-static bool own_use(hakai_ctx* c) {
-    if (!c->own_assembly || c->nmat > hk::kMaxLdsMats || c->nE <= 0)
-        return false;
-    const long long G0 = own_grid(c);
-    if (G0 <= 0) return false;
-    bool ok = c->own_built_g > 0;
-    if (c->own_for_g0 != G0) {  // not yet built (or found not to fit) for this grid
-        if (c->own_valid && own_materialize(c)) return false;  // (multi-GPU: step_once reports it)
-        // slots per block: what two blocks per CU leave next to the kernel's own LDS (the wider
-        // passes of S = 2 leave less)
-        const hk::OwnInput in{c->nE, c->nN, c->nEp, c->h_conn, c->h_ptr, c->h_inc0, c->max_inc,
-                              c->own_band_rows, c->own_pass_batches, hkc::comm_dn_nodes(c),
-                              {hk::own_slot_cap(c->elem_exact != 0, 1, c->nmat),
-                               hk::own_slot_cap(c->elem_exact != 0, 2, c->nmat)}};
-        hk::OwnSched sc;
-        hk::OwnPlan pl;
-        ok = hk::own_choose(in, G0, sc, pl) && own_upload(c, sc, pl);
-        if (!ok) {
-            hkc::own_free(c);
-            c->own_built_g = -2;
-        }
-        c->own_for_g0 = G0;
-    }
-    // The reference-order kernel's waves drift apart within a batch more than the fused kernel's, so
-    // its block waits at the pass barrier for its slowest wave; passes that load a second entry
-    // inside that barrier region (wide cross-sections) make the wait long, and there the fe path is
-    // faster for this kernel (C5 slab 1.12 against 1.41 ms per step, C4 2.46 against 3.25,
-    // profiles/r03_wave_units_sweep.log). own_assembly 2 uses the owner sums anyway (tests); a
-    // multi-GPU rank whose owner sums are live keeps them (its interface fix needs the rows).
-    if (ok && c->elem_exact && c->own_round2 > 0 && c->own_assembly == 1 && !(c->comm && c->own_valid))
-        return false;
-    return ok;
-}
-
-// One explicit step (the loop body :497-764). With c->g_trd set (graph capture) the kernels take
-// the step number from the device counter and the element kernel advances it. Phase bits: the
-// contact search parts A1, A2, A3 (hkc::contact_phase; one GPU: all of it in A1) and the rest
-// (contact phase B, nodal, BCs, element, exchange). An in-process group with multi-GPU contact runs
-// each part on every rank before the next (hakai_step_group).
-enum { kPhaseA1 = 1, kPhaseRest = 2, kPhaseA2 = 4, kPhaseA3 = 8, kPhaseAll = 15 };
-static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase = kPhaseAll) {
-    hipStream_t s = c->stream;
-    EventPair ep;
-    if (c->contact) {  // contact force into external_force (:500-560), search parts
-        const int part_bit[3] = {kPhaseA1, kPhaseA2, kPhaseA3};
-        for (int part = 1; part <= 3; ++part) {
-            if (!(phase & part_bit[part - 1]) || (part > 1 && !hkc::contact_multi(c))) continue;
-            hkc::prof_begin(c, HAKAI_K_CONTACT, &ep);
-            const int rc = hkc::contact_phase(c, part, t, d_time);
-            hkc::prof_end(c, &ep);
-            if (rc) return rc;
-        }
-    }
-    if (!(phase & kPhaseRest)) return 0;
-    const int par = c->cur;  // graph mode: this step reads counter slot 1-par, writes slot par
-    // nodal update (:562-567), Q from the previous step's element forces (:668-675)
-    hk::NodalArgs na;
-    na.u = c->d_u[c->cur];
-    na.u_pre_out = c->d_u[1 - c->cur];
-    na.mass = c->d_mass;
-    na.inc_ptr = c->d_inc_ptr;
-    na.inc = c->d_inc;
-    na.inc8 = c->d_inc8;
-    na.fe = c->d_fe;
-    // owner-computed assembly: Q from the previous element step's sums (else the fe gather)
-    const bool own = own_use(c);
-    if (c->own_valid && !own) {  // switched off (or the lists could not be rebuilt)
-        if (int r = own_materialize(c)) return r;
-    }
-    na.qbuf = c->q_from_buf ? c->d_qbuf : nullptr;
-    na.fext = nullptr;
-    na.nN = c->nN;
-    na.dt = d_time;
-    na.bc_of_node = nullptr;
-    const bool own_q = c->own_valid && !na.qbuf;
-    na.own_q = own_q ? c->d_own_q : nullptr;
-    na.own_rp = own_q ? c->d_own_rp : nullptr;
-    na.own_rows = own_q ? c->d_own_rows : nullptr;
-    na.own_ridx = own_q ? c->d_own_ridx : nullptr;
-    hk::BCArgs ba;
-    ba.dof = c->d_bc_dof;
-    ba.grp = c->d_bc_grp;
-    ba.val = c->d_bc_val;
-    ba.n = c->nbc;
-    ba.amp_n = c->d_amp_n;
-    ba.amp_off = c->d_amp_off;
-    ba.amp_t = c->d_amp_t;
-    ba.amp_v = c->d_amp_v;
-    ba.out = c->d_u[1 - c->cur];
-    ba.ct = t * d_time;
-    ba.t_rd = c->g_trd;
-    ba.dt = d_time;
-    ba.poison = c->d_poison;
-    na.poison = c->d_poison;
-    // one GPU, small mesh: the nodal kernel applies the BCs (multi-GPU redoes interface nodes
-    // after the nodal kernel, so the BCs must come after that)
-    // (fuse_bc 2: at any size; large meshes measured slower with the fe gather, see kFuseBcMaxNodes)
-    const bool fuse_bc = c->nbc > 0 && c->d_bc_of_node && c->fuse_bc && !c->comm &&
-                         (c->nN <= kFuseBcMaxNodes || c->fuse_bc == 2);
-    if (fuse_bc) {
-        na.bc_of_node = c->d_bc_of_node;
-        na.bc = ba;
-    }
-    int rc = 0;
-    if (c->contact) {  // multi-GPU search: event exchange and force sums
-        if (hkc::contact_multi(c)) {
-            hkc::prof_begin(c, HAKAI_K_CONTACT_SUM, &ep);
-            rc = hkc::contact_step_b(c);
-            hkc::prof_end(c, &ep);
-            if (rc) return rc;
-        }
-        na.fext = c->d_fext;
-    }
-    if (c->loads) {  // external loads, rigid walls: contact force + loads + walls -> the step's total external force
-        if ((rc = hkc::loads_step(c, t, d_time, na.fext))) return rc;
-        na.fext = c->d_ftot;  // = hkc::step_fext(c), what the interface fix takes too
-    }
-    rc = hkc::comm_pre_nodal(c);
-    if (rc) return rc;
-    if (c->hist && (rc = hkc::history_seed(c, na, s))) return rc;  // first step after a (re)start
-    hkc::prof_begin(c, HAKAI_K_NODAL, &ep);
-    HIPCHK(hk::launch_nodal(na, s));
-    hkc::prof_end(c, &ep);
-    // multi-GPU: interface nodes are redone with the cross-rank assembled Q
-    hkc::CommFix fix;  // what the fix read: the history hook forms the same Q at the nodes this rank owns
-    rc = hkc::comm_post_nodal(c, d_time, &fix);
-    if (rc) return rc;
-    // boundary conditions (:585-617)
-    if (c->nbc > 0 && !fuse_bc) {
-        hkc::prof_begin(c, HAKAI_K_BC, &ep);
-        HIPCHK(hk::launch_bc(ba, s));
-        hkc::prof_end(c, &ep);
-    }
-    // history output: this step's sums, from the Q the nodal update consumed (still intact)
-    if (c->hist && (rc = hkc::history_step(c, na, fix, t, c->g_trd, s))) return rc;
-    c->cur = 1 - c->cur;  // disp <- disp_new, disp_pre <- disp (:626-627)
-    c->q_from_buf = false;
-    // element update (:662-667) + triaxiality (:677) + ductile deletion (:684-764)
-    hk::ElemArgs ea = elem_args(c);
-    ea.step_i = (int)t;
-    if (own) {
-        ea.own = c->own_s;
-        ea.own_grid = (int)c->own_built_g;
-        ea.own_seq = c->d_own_seq;
-        ea.own_bstart = c->d_own_bstart;
-        ea.own_off = c->d_own_off;
-        ea.own_list = reinterpret_cast<const int4*>(c->d_own_list);
-        ea.own_nop = c->own_nop;
-        ea.own_slots = c->own_slots;
-        ea.own_q = c->d_own_q;
-        ea.own_rows = c->d_own_rows;
-        ea.own_dump = c->d_own_dump;
-    }
-    if (c->g_trd) {
-        ea.t_rd = c->g_trd;
-        ea.t_wr = c->d_tstep + par;
-    }
-    hkc::prof_begin(c, HAKAI_K_ELEMENT, &ep);
-    HIPCHK(hk::launch_element(ea, c->has_ductile, last, s));
-    hkc::prof_end(c, &ep);
-    c->own_valid = own;
-    c->own_steps += own ? 1 : 0;
-    c->fe_ok = !own || last;  // owner assembly stores fe on a call's last step only
-    c->triax_ok = last;
-    rc = hkc::comm_post_element(c, (long long)t);
-    if (rc) return rc;
-    rc = hkc::contact_post_step(c);
-    if (rc) return rc;
-    c->steps_done++;
-    c->last_dt = d_time;
-    return 0;
-}
-
-// A run of steps starting at t can come from a graph: same launch sequence every step, nothing
-// host-side that depends on the step (no multi-GPU exchange, no profiling events, no uploaded Q),
-// and contact in its steady state. The step number comes from a device counter; every pointer
-// argument is fixed for a given starting parity (cur), so one graph per parity serves the whole
-// run. A failed capture leaves the context's host state advanced: the call returns the error.
-static bool graph_eligible(const hakai_ctx* c, double t) {
-    // (owner-computed assembly: only once the previous step left its sums, so every captured nodal
-    // update reads them)
-    return c->graph && !c->comm && !c->prof && !c->q_from_buf && c->nE > 0 && hkc::contact_graph_ok(c, t) &&
-           !hkc::history_needs_seed(c) &&
-           c->own_valid == own_use(const_cast<hakai_ctx*>(c));
-}
-
-static int step_graph(hakai_ctx* c, double t, double d_time, int len) {
-    hipStream_t s = c->stream;
-    const int p0 = c->cur;
-    const int gi = len == 2 ? 1 : 0;
-    hipGraphExec_t& ge = c->g_exec[gi][p0];
-    if (!c->d_tstep) HIPCHK(dalloc(&c->d_tstep, 2));
-    if (c->tdev_next != (long long)t) HIPCHK(hk::launch_set_step(c->d_tstep + (1 - p0), t - 1.0, s));
-    if (ge && (c->g_epoch[gi][p0] != c->epoch || c->g_dt[gi][p0] != d_time || c->g_len[gi][p0] != len)) {
-        HIPCHK(hipStreamSynchronize(s));
-        (void)hipGraphExecDestroy(ge);
-        ge = nullptr;
-    }
-    if (!ge) {
-        // capture the steps; their host-side state changes happen here, as in stream mode
-        hipGraph_t g = nullptr;
-        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = 0;
-        for (int k = 0; k < len && !rc; ++k) {
-            c->g_trd = c->d_tstep + (1 - c->cur);
-            rc = step_once(c, t + k, d_time, false);
-        }
-        c->g_trd = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc;
-        }
-        if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture (step graph)");
-        e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) {
-            ge = nullptr;
-            return hip_fail(e, "hipGraphInstantiate (step graph)");
-        }
-        c->g_epoch[gi][p0] = c->epoch;
-        c->g_dt[gi][p0] = d_time;
-        c->g_len[gi][p0] = len;
-    } else {  // replay the host-side state changes of the captured steps
-        hkc::contact_graph_advance(c, t + len - 1);
-        c->q_from_buf = false;
-        c->own_steps += c->own_valid ? len : 0;  // captured in the steady state: every step or none
-        c->fe_ok = !c->own_valid;                 // (a captured step is never a call's last)
-        c->triax_ok = false;
-        c->steps_done += len;
-        c->last_dt = d_time;
-    }
-    HIPCHK(hipGraphLaunch(ge, s));
-    c->tdev_next = (long long)t + len;
-    c->graph_steps += len;
-    return 0;
-}
-
-// The host's view of a context before a stepping call's first step (after any owner-assembly
-// re-plan, which hands the last sums over unchanged): what an overflow on that step rolls back to.
-struct CallSnap {
-    int cur = 0;
-    long long done = 0;
-    bool fe_ok = true, triax_ok = true, own_valid = false, q_from_buf = false;
-    bool comm_pending = false;  // the interface exchange the call's first nodal update consumes
-    int comm_par = 0;
-};
-static CallSnap call_snap(const hakai_ctx* c) {
-    CallSnap s;
-    hkc::comm_pending_get(c, &s.comm_pending, &s.comm_par);
-    s.cur = c->cur;
-    s.done = c->steps_done;
-    s.fe_ok = c->fe_ok;
-    s.triax_ok = c->triax_ok;
-    s.own_valid = c->own_valid;
-    s.q_from_buf = c->q_from_buf;
-    return s;
-}
-
-// End of a stepping call: the contact overflow check. An overflow poisoned step p: the device's
-// state-writing kernels of steps p.. were no-ops, so the device holds the state after step p-1;
-// bring the host's view back to that step.
-static int finish_call(hakai_ctx* c, double t_first, int64_t n_steps, const CallSnap& s0) {
-    const int rc = hkc::contact_check(c);
-    if (rc && c->contact) {
-        int pz[2] = {0, 0};
-        HIPCHK(hipMemcpy(pz, c->d_poison, sizeof pz, hipMemcpyDeviceToHost));
-        if (pz[0]) {
-            c->poison_step = pz[1];
-            const long long good = (long long)pz[1] - (long long)t_first;  // steps of this call that ran
-            const bool rolled = good >= 0 && good <= n_steps;
-            if (rolled) {
-                c->cur = (good & 1) ? 1 - s0.cur : s0.cur;
-                c->steps_done = s0.done + good;
-                if (good == 0) {  // nothing of the call ran: where the Q of the next nodal update is
-                    c->fe_ok = s0.fe_ok;
-                    c->triax_ok = s0.triax_ok;
-                    c->own_valid = s0.own_valid;
-                    c->q_from_buf = s0.q_from_buf;
-                } else {  // the call's last step (the one that stores fe and triax) did not run
-                    c->fe_ok = !c->own_valid;
-                    c->triax_ok = false;
-                }
-                hkc::comm_rollback(c, good > 0, (long long)pz[1] - 1, s0.comm_pending, s0.comm_par);
-            }
-            hkc::graph_invalidate(c);
-            hkc::contact_after_overflow(c, c->steps_done);
-            // a poison step outside this call rolled nothing back: never run the call again from it
-            if (!rolled) (void)hkc::contact_exchange_retry(c);
-            HIPCHK(hipMemset(c->d_poison, 0, 2 * sizeof(int)));
-            const std::string msg = hakai_last_error();
-            return fail(rc, "%s; step %d was not applied: the state is that after step %d", msg.c_str(), pz[1],
-                        pz[1] - 1);
-        }
-    }
-    return rc;
-}
-
-static int step_call(hakai_ctx* c, double t_first, int64_t n_steps, double d_time);
-static constexpr int kExchangeRetries = 8;
-
-int hakai_step(hakai_ctx* c, double t_first, int64_t n_steps, double d_time) {
-    if (!c) return fail(HAKAI_ERR_ARG, "null");
-    if (!c->model_ok || !c->state_ok) return fail(HAKAI_ERR_STATE, "step before upload_model/reset_state");
-    if (n_steps < 0 || !(d_time > 0)) return fail(HAKAI_ERR_ARG, "step: n_steps=%lld d_time=%g", (long long)n_steps, d_time);
-    if (n_steps > 1 && hkc::comm_is_local(c))
-        return fail(HAKAI_ERR_ARG, "step: an in-process group is stepped one step per call, rank by rank");
-    // a contact rank of an in-process group needs its peers' phases between its own: refused before
-    // any work, so its contact state (tsel parity, touched lists, bin headers) stays in step with them
-    if (hkc::comm_is_local(c) && hkc::contact_multi(c) && hkc::comm_size(c) > 1)
-        return fail(HAKAI_ERR_STATE, "step: rank %d of an in-process group with multi-GPU contact is stepped by "
-                    "hakai_step_group only", hkc::comm_rank(c));
-    HIPCHK(hipSetDevice(c->device));
-    // a step that overflowed a multi-GPU contact exchange runs again once its capacity has grown
-    // (every rank takes the same decision from the same gathered counts)
-    for (int attempt = 0;; ++attempt) {
-        const int rc = step_call(c, t_first, n_steps, d_time);
-        if (!rc || attempt >= kExchangeRetries || !hkc::contact_exchange_retry(c)) return rc;
-        ++c->exchange_retries;
-        n_steps -= (int64_t)(c->poison_step - (long long)t_first);
-        t_first = (double)c->poison_step;
-    }
-}
-
-static int step_call(hakai_ctx* c, double t_first, int64_t n_steps, double d_time) {
-    (void)own_use(c);  // owner-assembly lists are built here, never inside a graph capture
-    const CallSnap s0 = call_snap(c);
-    int64_t it = 0;
-    while (it < n_steps) {
-        const double t = t_first + (double)it;
-        int rc;
-        // the call's last step stays in stream mode: it also stores triaxiality for downloads
-        // (eligibility of step t implies it for the steps after it: step t clears every one-off
-        // condition)
-        const int len = (c->graph > 2 && it + c->graph < n_steps) ? c->graph : 2;
-        if (c->graph && it + len < n_steps && graph_eligible(c, t)) {
-            rc = step_graph(c, t, d_time, len);
-            it += len;
-        } else {
-            rc = step_once(c, t, d_time, it == n_steps - 1);
-            c->tdev_next = -1;
-            ++it;
-        }
-        if (rc) return rc;
-    }
-    return finish_call(c, t_first, n_steps, s0);
-}
-
-static int step_group_call(hakai_ctx** ctxs, int32_t n, double t_first, int64_t n_steps, double d_time) {
-    std::vector<CallSnap> s0(n);
-    for (int r = 0; r < n; ++r) {
-        (void)own_use(ctxs[r]);  // (re-plans here, as hakai_step does, not inside the first step)
-        s0[r] = call_snap(ctxs[r]);
-    }
-    // per step: each contact part on every rank before the next part on any, then the rest
-    const int phases[4] = {kPhaseA1, kPhaseA2, kPhaseA3, kPhaseRest};
-    for (int64_t it = 0; it < n_steps; ++it) {
-        const double t = t_first + (double)it;
-        const bool last = it == n_steps - 1;
-        for (int ph : phases)
-            for (int r = 0; r < n; ++r) {
-                // group_serial 2: the phase is enqueued behind a fixed sleep (≈0.3 ms), so its kernels
-                // run back to back as in a pipelined run, not at the host's enqueue pace
-                if (ctxs[0]->group_serial == 2) HIPCHK(hk::launch_hold(96, ctxs[r]->stream));
-                if (int rc = step_once(ctxs[r], t, d_time, last, ph)) return rc;
-                if (ph == kPhaseRest) ctxs[r]->tdev_next = -1;
-                if (ctxs[0]->group_serial) HIPCHK(hipStreamSynchronize(ctxs[r]->stream));
-            }
-    }
-    int first = 0;
-    for (int r = 0; r < n; ++r) {
-        const int rc = finish_call(ctxs[r], t_first, n_steps, s0[r]);
-        if (rc && !first) first = rc;
-    }
-    return first;
-}
-
-int hakai_step_group(hakai_ctx** ctxs, int32_t n, double t_first, int64_t n_steps, double d_time) {
-    if (!ctxs || n <= 0) return fail(HAKAI_ERR_ARG, "step_group: no contexts");
-    if (n_steps < 0 || !(d_time > 0)) return fail(HAKAI_ERR_ARG, "step_group: n_steps=%lld d_time=%g",
-                                                  (long long)n_steps, d_time);
-    for (int r = 0; r < n; ++r) {
-        hakai_ctx* c = ctxs[r];
-        if (!c) return fail(HAKAI_ERR_ARG, "step_group: null context %d", r);
-        if (!c->model_ok || !c->state_ok) return fail(HAKAI_ERR_STATE, "step_group: rank %d has no model/state", r);
-        if (n > 1 && (!c->comm || hkc::comm_rank(c) != r || hkc::comm_size(c) != n ||
-                      hkc::comm_peer_ctx(c, r) != c))
-            return fail(HAKAI_ERR_ARG, "step_group: context %d is not rank %d of an in-process group of %d", r, r, n);
-        hkc::graph_invalidate(c);
-    }
-    HIPCHK(hipSetDevice(ctxs[0]->device));
-    for (int attempt = 0;; ++attempt) {
-        const int rc = step_group_call(ctxs, n, t_first, n_steps, d_time);
-        if (!rc || attempt >= kExchangeRetries) return rc;
-        bool retry = true;  // (the same on every rank: they read the same headers)
-        for (int r = 0; r < n; ++r) retry = hkc::contact_exchange_retry(ctxs[r]) && retry;
-        if (!retry) return rc;
-        const long long p = ctxs[0]->poison_step;
-        for (int r = 1; r < n; ++r)  // every rank read the same headers: the same step, or no retry
-            if (ctxs[r]->poison_step != p)
-                return fail(rc, "step_group: ranks disagree on the poisoned step (rank 0: %lld, rank %d: %lld)", p, r,
-                            ctxs[r]->poison_step);
-        for (int r = 0; r < n; ++r) ++ctxs[r]->exchange_retries;
-        n_steps -= (int64_t)(p - (long long)t_first);
-        t_first = (double)p;
-    }
-}
-
-int hakai_graph_steps(hakai_ctx* c, int64_t* n) {
-    if (!c || !n) return fail(HAKAI_ERR_ARG, "null");
-    *n = c->graph_steps;
-    return 0;
-}
-
 int hakai_stat(hakai_ctx* c, const char* key, int64_t* value) {
     if (!c || !key || !value) return fail(HAKAI_ERR_ARG, "null");
     if (!std::strcmp(key, "graph_steps")) *value = c->graph_steps;
-    else if (!std::strcmp(key, "own_steps")) *value = c->own_steps;
     else if (!std::strcmp(key, "exchange_retries")) *value = c->exchange_retries;
-    else if (!std::strcmp(key, "own_rows")) *value = c->own_built_g > 0 ? c->own_rows : -1;
-    else if (!std::strcmp(key, "own_entries")) *value = c->own_built_g > 0 ? c->own_entries : -1;
-    else if (!std::strcmp(key, "own_superbatch")) *value = c->own_built_g > 0 ? c->own_s : 0;
-    else if (!std::strcmp(key, "own_round2")) *value = c->own_built_g > 0 ? c->own_round2 : 0;
-    else if (!std::strcmp(key, "own_slots")) *value = c->own_built_g > 0 ? c->own_slots : 0;
-    else if (!std::strcmp(key, "own_banded")) *value = c->own_built_g > 0 ? c->own_banded : 0;
-    else if (!std::strcmp(key, "own_grid")) *value = c->own_built_g > 0 ? c->own_built_g : 0;
+    else if (!std::strncmp(key, "own_", 4)) return hkc::own_stat(c, key, value);
     else return fail(HAKAI_ERR_ARG, "unknown stat '%s'", key);
     return 0;
 }
@@ -1372,20 +897,8 @@ int hakai_set_tuning(hakai_ctx* c, const char* key, int64_t value) {
     }
     if (!std::strcmp(key, "elem_exact")) {
         if (value != 0 && value != 1) return fail(HAKAI_ERR_ARG, "elem_exact must be 0 or 1");
-        if (c->elem_exact != (int)value && c->own_for_g0 != -1) {
-            // the owner-assembly plan was sized for the other kernel's LDS budget (the reference-order
-            // kernel leaves fewer slots): re-planned before the next step (own_use; one context hands
-            // the last sums over through own_materialize). A multi-GPU rank whose sums are live cannot
-            // re-plan mid-run (its next interface fix reads the rows): it keeps a plan that fits the
-            // new kernel, else the switch is refused.
-            if (!(c->comm && c->own_valid)) {
-                c->own_for_g0 = -1;
-            } else if (c->own_built_g > 0 && c->own_slots > hk::own_slot_cap(value != 0, c->own_s, c->nmat)) {
-                return fail(HAKAI_ERR_STATE, "elem_exact: the owner-assembly lists of this multi-GPU rank need %d LDS "
-                            "slots, more than the %s kernel has; switch between calls after hakai_upload_state / "
-                            "hakai_reset_state", c->own_slots, value ? "reference-order" : "fused");
-            }
-        }
+        if (c->elem_exact != (int)value)  // the owner-assembly plan was sized for the other kernel
+            if (int r = hkc::own_tuning(c, key, value)) return r;
         c->elem_exact = (int)value;
         return 0;
     }
@@ -1401,23 +914,7 @@ int hakai_set_tuning(hakai_ctx* c, const char* key, int64_t value) {
         }
         return c->d_inc8 ? 0 : fail(HAKAI_ERR_STATE, "padded incidence table unavailable (>8 incidences)");
     }
-    if (!std::strcmp(key, "own_assembly")) {  // owner-computed node sums in the element kernel
-        if (value < 0 || value > 2) return fail(HAKAI_ERR_ARG, "own_assembly must be 0, 1 or 2");
-        c->own_assembly = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "own_pass_batches")) {  // batches per owner summing pass (0: planned)
-        if (value < 0 || value > 2) return fail(HAKAI_ERR_ARG, "own_pass_batches must be 0, 1 or 2");
-        if (c->own_pass_batches != (int)value) c->own_for_g0 = -1;  // re-plan at the next step
-        c->own_pass_batches = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "own_band_rows")) {  // row-band height of the banded owner schedule (0: planned)
-        if (value < 0 || value > 4096) return fail(HAKAI_ERR_ARG, "own_band_rows must be in [0, 4096]");
-        if (c->own_band_rows != (int)value) c->own_for_g0 = -1;  // re-plan at the next step
-        c->own_band_rows = (int)value;
-        return 0;
-    }
+    if (!std::strncmp(key, "own_", 4)) return hkc::own_tuning(c, key, value);
     if (!std::strcmp(key, "graph")) {
         if (value < 0 || value > 1024 || (value & 1)) return fail(HAKAI_ERR_ARG, "graph must be 0 or an even step count <= 1024");
         c->graph = (int)value;
@@ -1447,7 +944,7 @@ int hakai_negative_jacobians(hakai_ctx* c, int64_t* n) {
     if (!c->state_ok) return fail(HAKAI_ERR_STATE, "negative_jacobians without state");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemsetAsync(c->d_negjac, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(hk::launch_negjac(elem_args(c), c->d_negjac, c->stream));
+    HIPCHK(hk::launch_negjac(hkc::elem_args(c, c->sv.cur), c->d_negjac, c->stream));
     unsigned long long v = 0;
     HIPCHK(hipMemcpyAsync(&v, c->d_negjac, sizeof v, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1546,7 +1043,7 @@ int hakai_stress_hexa(int device, int64_t nNode, int64_t nElement, double* Qe, d
     double* d_vol = nullptr;
     HIPCHK(dalloc(&d_vol, (size_t)c->nEp));
     HIPCHK(hipMemsetAsync(c->d_fe, 0, 24 * (size_t)nElement * sizeof(double), s));
-    hk::ElemArgs ea = elem_args(c);
+    hk::ElemArgs ea = hkc::elem_args(c, c->sv.cur);
     ea.vol = d_vol;
     ea.pipe_blocks = 0;
     HIPCHK(hk::launch_element(ea, false, false, s));
@@ -1555,8 +1052,6 @@ int hakai_stress_hexa(int device, int64_t nNode, int64_t nElement, double* Qe, d
     HIPCHK(hipMemcpyAsync(vol.data(), d_vol, vol.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     dfree(d_vol);
-    c->steps_done = 1;
-    c->last_dt = 1.0;
     hakai_state_t out;
     std::memset(&out, 0, sizeof out);
     out.integ_stress = integ_stress;

@@ -66,14 +66,11 @@ static std::map<long long, LocalGroup*> g_groups;
 
 }  // namespace hkc
 
+using hkc::dalloc;
+using hkc::dfree;
 using hkc::fail;
 using hkc::hip_fail;
 
-#define HIPCHK(x)                                      \
-    do {                                               \
-        hipError_t _e = (x);                           \
-        if (_e != hipSuccess) return hip_fail(_e, #x); \
-    } while (0)
 #define NCCLCHK(x)                                                                        \
     do {                                                                                  \
         ncclResult_t _r = (x);                                                            \
@@ -229,18 +226,6 @@ __global__ void k_fix_own(const int* up, int n_up, const int* dn, int n_dn, cons
         const double f = fext ? fext[3 * n + c] : 0.0;
         out[3 * n + c] = inv * (f - Q[c] + mdt2 * (2.0 * uc - up_) + dC / 2.0 / dt * up_);
     }
-}
-
-template <class T>
-hipError_t dalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc((void**)p, n * sizeof(T));
-}
-template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
 }
 
 void free_iface(hkc::Comm* m) {
@@ -442,7 +427,7 @@ int comm_pre_nodal(hakai_ctx* c) {
     if (!m || m->n_up + m->n_dn == 0 || !m->pending) return 0;
     const int n = m->n_up + m->n_dn;
     hipLaunchKernelGGL(k_save_upre, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn, m->n_dn,
-                       c->d_u[1 - c->cur], m->d_saved);
+                       c->d_u[1 - c->sv.cur], m->d_saved);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -452,7 +437,7 @@ int comm_post_nodal(hakai_ctx* c, double d_time, CommFix* fix) {
     if (!m || m->n_up + m->n_dn == 0 || !m->pending) return 0;
     m->pending = false;
     const int par = m->pending_par;
-    if (fix && !c->q_from_buf) {  // one of the two fix kernels below runs, on these buffers
+    if (fix && c->sv.q != QSrc::Buf) {  // one of the two fix kernels below runs, on these buffers
         fix->ran = true;
         fix->n_up = m->n_up;
         fix->nslot = m->nslot;
@@ -479,18 +464,19 @@ int comm_post_nodal(hakai_ctx* c, double d_time, CommFix* fix) {
                                   hipMemcpyDeviceToDevice, c->stream));
         }
     }
-    if (!c->q_from_buf && c->own_valid) {  // the previous element step summed node forces itself
+    if (c->sv.q == QSrc::Own) {  // the previous element step summed node forces itself
         const int n = m->n_up + m->n_dn;
+        const OwnSums o = own_sums(c);
         hipLaunchKernelGGL(k_fix_own, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn,
-                           m->n_dn, c->d_own_rp, c->d_own_ridx, c->d_own_rows, m->nslot, m->d_up_sendP[par],
-                           m->d_up_recvC, m->d_dn_recvP, m->d_saved, c->d_u[c->cur], c->d_u[1 - c->cur], c->d_mass,
+                           m->n_dn, o.rp, o.ridx, o.rows, m->nslot, m->d_up_sendP[par],
+                           m->d_up_recvC, m->d_dn_recvP, m->d_saved, c->d_u[c->sv.cur], c->d_u[1 - c->sv.cur], c->d_mass,
                            step_fext(c), d_time, c->d_poison);
         HIPCHK(hipGetLastError());
-    } else if (!c->q_from_buf) {  // an uploaded Q already holds the global sum
+    } else if (c->sv.q == QSrc::Fe) {  // an uploaded Q already holds the global sum
         const int n = m->n_up + m->n_dn;
         hipLaunchKernelGGL(k_fix, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn, m->n_dn,
                            c->d_inc_ptr, c->d_inc, c->d_fe, m->nslot, m->d_up_sendP[par], m->d_up_recvC, m->d_dn_recvP,
-                           m->d_saved, c->d_u[c->cur], c->d_u[1 - c->cur], c->d_mass, step_fext(c),
+                           m->d_saved, c->d_u[c->sv.cur], c->d_u[1 - c->sv.cur], c->d_mass, step_fext(c),
                            d_time, c->d_poison);
         HIPCHK(hipGetLastError());
     }
@@ -503,11 +489,11 @@ int comm_post_element(hakai_ctx* c, long long step) {
     if (!m || m->n_up + m->n_dn == 0) return 0;
     const int par = (int)(step & 1);
     const int n = m->n_up + m->n_dn;
-    if (c->own_valid)  // this step's element kernel summed the node forces (owner-computed assembly)
+    if (c->sv.q == QSrc::Own) {  // this step's element kernel summed the node forces (owner-computed assembly)
+        const OwnSums o = own_sums(c);
         hipLaunchKernelGGL(k_pack_own, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn,
-                           m->n_dn, c->d_own_rp, c->d_own_ridx, c->d_own_rows, c->d_own_q, m->nslot,
-                           m->d_up_sendP[par], m->d_dn_sendC[par]);
-    else
+                           m->n_dn, o.rp, o.ridx, o.rows, o.q, m->nslot, m->d_up_sendP[par], m->d_dn_sendC[par]);
+    } else
         hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_up, m->n_up, m->d_dn, m->n_dn,
                            c->d_inc_ptr, c->d_inc, c->d_fe, m->nslot, m->d_up_sendP[par], m->d_dn_sendC[par]);
     HIPCHK(hipGetLastError());
@@ -659,9 +645,7 @@ int hakai_set_interface(hakai_ctx* c, int64_t n_shared, const int64_t* local_nod
     m->h_dn = dn;
     m->h_up = up;
     m->iface_set = true;
-    c->own_built_g = -1;  // owner-assembly lists export every dn node's contributions: rebuilt
-    c->own_for_g0 = -1;
-    c->own_valid = false;
+    hkc::own_invalidate(c);  // owner-assembly lists export every dn node's contributions: rebuilt
     HIPCHK(dalloc(&m->d_up, up.size()));
     HIPCHK(dalloc(&m->d_dn, dn.size()));
     for (int p = 0; p < 2; ++p) {

@@ -38,12 +38,6 @@
 using hkc::fail;
 using hkc::hip_fail;
 
-#define HIPCHK(x)                                      \
-    do {                                               \
-        hipError_t _e = (x);                           \
-        if (_e != hipSuccess) return hip_fail(_e, #x); \
-    } while (0)
-
 namespace {
 
 using namespace hkc::ck;
@@ -910,8 +904,8 @@ StepIn step_in(hakai_ctx* c, double t, double d_time) {
     Contact* C = c->contact;
     StepIn in;
     in.coord = c->d_coord;
-    in.u = c->d_u[c->cur];
-    in.u_pre = c->d_u[1 - c->cur];
+    in.u = c->d_u[c->sv.cur];
+    in.u_pre = c->d_u[1 - c->sv.cur];
     in.flag = c->d_flag;
     in.conn = c->d_conn;
     in.mass = c->d_mass;
@@ -957,7 +951,7 @@ void launch_reset(hakai_ctx* c, unsigned long long* bbox, bool rebuild, const in
                   int* zero_hdr) {
     Contact* C = c->contact;
     hipLaunchKernelGGL(k_ct_reset, dim3(C->g_reset), dim3(kB), 0, c->stream, bbox, C->npairs, C->d_ctl, C->d_evs,
-                       C->d_ccnt, rebuild ? 1 : 0, del_any, t, c->g_trd, C->d_touched[1 - C->tsel], C->tsel, c->d_fext,
+                       C->d_ccnt, rebuild ? 1 : 0, del_any, t, c->gr.trd, C->d_touched[1 - C->tsel], C->tsel, c->d_fext,
                        g2l, zero_hdr);
 }
 
@@ -982,7 +976,7 @@ void live_append(hakai_ctx* c, const int* del_step, int t) {
     Contact* C = c->contact;
     if (C->ntile == 0) return;
     hipLaunchKernelGGL(k_ct_append, dim3(256), dim3(64), 0, c->stream, C->d_ctl, C->d_dlist, append_in(C), del_step, t,
-                       c->g_trd, C->d_reg, C->d_ni_live, C->d_nj_live, C->d_tri_live);
+                       c->gr.trd, C->d_reg, C->d_ni_live, C->d_nj_live, C->d_tri_live);
 }
 
 void launch_boxes(hakai_ctx* c, const StepIn& in, unsigned long long* bbox) {
@@ -1018,7 +1012,7 @@ static int step_start(hakai_ctx* c, double t, double d_time) {
     const bool fused = C->small && C->fuse_small;
     if (fused && !rebuild) {
         hipLaunchKernelGGL(k_ct_prologue1, dim3(1), dim3(kSmallThreads), 0, s, C->d_bbox, C->npairs, C->d_ctl, C->d_evs,
-                           C->d_ccnt, del_any, in.t, c->g_trd, C->d_touched[1 - C->tsel], C->tsel, c->d_fext, del_step,
+                           C->d_ccnt, del_any, in.t, c->gr.trd, C->d_touched[1 - C->tsel], C->tsel, c->d_fext, del_step,
                            (int)C->nE, C->d_dlist, append_in(C), C->d_reg, C->d_ni_live, C->d_nj_live, C->d_tri_live,
                            C->ntile > 0 ? 1 : 0);
     } else {
@@ -1026,7 +1020,7 @@ static int step_start(hakai_ctx* c, double t, double d_time) {
         if (rebuild) live_rebuild(c, del_step, in.t);
         if (C->ntile > 0)
             hipLaunchKernelGGL(k_ct_find_del, dim3(C->g_del), dim3(kB), 0, s, C->d_ctl, del_step, (int)C->nE, in.t,
-                               c->g_trd, C->d_dlist);
+                               c->gr.trd, C->d_dlist);
         live_append(c, del_step, in.t);
     }
     launch_boxes(c, in, C->d_bbox);
@@ -1067,13 +1061,13 @@ static int search(hakai_ctx* c, const StepIn& in, bool fused) {
     if (fused) {  // small decks: count, alloc, scatter and sum in one workgroup
         hipLaunchKernelGGL(k_ct_gather1, dim3(1), dim3(kSmallThreads), 0, s, C->d_ctl, C->d_evs, C->cap / kEvShards,
                            C->d_ev_nodes, C->d_ev_f, C->d_cnt, C->d_touched[tsel], C->d_tpos, tsel, c->d_poison,
-                           in.t, c->g_trd, C->d_toff, C->d_tcnt, C->d_terms, c->d_fext);
+                           in.t, c->gr.trd, C->d_toff, C->d_tcnt, C->d_terms, c->d_fext);
         HIPCHK(hipGetLastError());
         C->use_velo0 = false;
         return 0;
     }
     hipLaunchKernelGGL(k_ct_count, dim3(ge), dim3(kB), 0, s, C->d_ctl, C->d_evs, C->cap / kEvShards, C->d_ev_nodes,
-                       C->d_cnt, C->d_touched[tsel], C->d_tpos, tsel, c->d_poison, in.t, c->g_trd);
+                       C->d_cnt, C->d_touched[tsel], C->d_tpos, tsel, c->d_poison, in.t, c->gr.trd);
     launch_alloc(c);
     hipLaunchKernelGGL(k_ct_scatter, dim3(ge), dim3(kB), 0, s, C->d_ctl, C->d_evs, C->cap / kEvShards, C->d_ev_nodes,
                        C->d_ev_f, C->d_toff, C->d_tpos, C->d_cnt, C->d_terms);
@@ -1358,7 +1352,7 @@ int contact_setup(hakai_ctx* c, const hkc::ContactInput& in, hkc::ContactPlan& P
         HIPCHK(hipMemcpyAsync(C->d_velo0, c->h_velo0.data(), 3 * (size_t)c->nN * sizeof(double), hipMemcpyHostToDevice, s));
     else
         HIPCHK(hipMemsetAsync(C->d_velo0, 0, 3 * (size_t)c->nN * sizeof(double), s));
-    C->use_velo0 = c->steps_done == 0 || !c->h_velo0.empty();
+    C->use_velo0 = c->sv.steps_done == 0 || !c->h_velo0.empty();
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }

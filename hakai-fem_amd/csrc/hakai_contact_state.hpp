@@ -1,7 +1,7 @@
 // hakai_contact_state.hpp -- the contact search state (hkc::Contact), the records its hash grid
-// holds, the owning device buffer, and what crosses between the two translation units of the
-// contact search: hakai_contact.hip (the one-GPU step, setup, the C entry points) and
-// hakai_contact_xr.hip (the owner-computed multi-GPU search, hkc::Xrank).
+// holds, and what crosses between the two translation units of the contact search:
+// hakai_contact.hip (the one-GPU step, setup, the C entry points) and hakai_contact_xr.hip (the
+// owner-computed multi-GPU search, hkc::Xrank). Its device arrays are DevBufs (hakai_devmem.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,46 +11,6 @@
 #include "hakai_internal.hpp"
 
 namespace hkc {
-
-// A device array that frees itself: move-only, converts to its pointer at launch sites.
-template <class T>
-class DevBuf {
-  public:
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) {
-            free();
-            p_ = o.p_;
-            o.p_ = nullptr;
-        }
-        return *this;
-    }
-    ~DevBuf() { free(); }
-    void free() {
-        if (p_) (void)hipFree((void*)p_);
-        p_ = nullptr;
-    }
-    // n elements (at least one), uninitialised; a held array is freed first
-    hipError_t alloc(size_t n) {
-        free();
-        const hipError_t e = hipMalloc((void**)&p_, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) p_ = nullptr;
-        return e;
-    }
-    hipError_t upload(const std::vector<T>& v, hipStream_t s) {
-        const hipError_t e = alloc(v.size());
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpyAsync(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
-    }
-    operator T*() const { return p_; }
-    T* get() const { return p_; }
-
-  private:
-    T* p_ = nullptr;
-};
 
 struct Xrank;  // multi-GPU state (hakai_contact_xr.hip)
 namespace ck {

@@ -16,12 +16,6 @@
 using hkc::fail;
 using hkc::hip_fail;
 
-#define HIPCHK(x)                                      \
-    do {                                               \
-        hipError_t _e = (x);                           \
-        if (_e != hipSuccess) return hip_fail(_e, #x); \
-    } while (0)
-
 namespace hkc {
 
 // Multi-GPU contact (hakai_set_contact_global, §8f-3): owner-computed search. Every rank sets up

@@ -32,12 +32,6 @@
 using hkc::fail;
 using hkc::hip_fail;
 
-#define HIPCHK(x)                                           \
-    do {                                                    \
-        hipError_t _e = (x);                                \
-        if (_e != hipSuccess) return hip_fail(_e, #x);      \
-    } while (0)
-
 namespace hk {
 
 constexpr int kHB = 256;                                // nodes per chunk = threads per block

@@ -7,6 +7,10 @@
 
 #include "../../include/hakai_hip.h"
 #include "hakai_device.hpp"
+#include "hakai_devmem.hpp"
+#include "hakai_kernels.hpp"
+#include "hakai_own.hpp"
+#include "hakai_step_view.hpp"
 
 namespace hkc {
 struct Comm;     // multi-GPU state (hakai_comm.cpp)
@@ -36,8 +40,8 @@ struct hakai_ctx {
     // model
     long long nN = 0, nE = 0, nEp = 0, ld = 0;
     double* d_coord = nullptr;
-    double* d_u[2] = {nullptr, nullptr};
-    int cur = 0;  // d_u[cur] = disp, d_u[1-cur] = disp_pre
+    double* d_u[2] = {nullptr, nullptr};  // d_u[sv.cur] = disp, d_u[1-sv.cur] = disp_pre
+    hkc::StepView sv;            // the host's view of the stepping state (hakai_step_view.hpp)
     double* d_mass = nullptr;
     int* d_conn = nullptr;
     int* d_flag = nullptr;
@@ -83,15 +87,8 @@ struct hakai_ctx {
     int* d_bc_of_node = nullptr; // [nN] first resolved BC entry of each node (-1 none)
     int fuse_bc = 1;             // tuning "fuse_bc": the nodal kernel applies the BCs (one GPU)
     // state extras
-    double* d_qbuf = nullptr;
-    bool q_from_buf = false;
-    // fe / triax hold the current state's element forces / triaxiality. With owner-computed assembly
-    // the element kernel stores fe (and, in both modes, triax) only on a call's last step, so after
-    // a call whose later steps a contact overflow turned into no-ops they are stale: the Qe and
-    // triaxiality downloads then fail (HAKAI_ERR_STATE) until a step has run (Q stays available).
-    bool fe_ok = true, triax_ok = true;
+    double* d_qbuf = nullptr;    // the uploaded Q (sv.q == QSrc::Buf: the next nodal update reads it)
     std::vector<double> h_velo0;  // velo as uploaded / set by IC, valid until the first step
-    long long steps_done = 0;
     double last_dt = 0.0;
     int* d_del_step = nullptr;   // [nEp+2] deletion step per element (0 = never), [nEp] dump slot,
                                  // [nEp+1] last step in which any element was deleted
@@ -121,40 +118,18 @@ struct hakai_ctx {
     // (cur), plus a 2-step graph for the tail; the step number is read from a device counter
     // instead of kernel arguments. Slot [g][p]: g 0 = `graph` steps, 1 = 2 steps; p = parity.
     double* d_tstep = nullptr;         // [2] counter slots (slot 1-cur: previous step's number)
-    const double* g_trd = nullptr;     // non-null while a step is captured: its counter slot
-    hipGraphExec_t g_exec[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    double g_dt[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-    long long g_epoch[2][2] = {{-1, -1}, {-1, -1}};
-    int g_len[2][2] = {{0, 0}, {0, 0}};
+    struct StepGraphs {
+        const double* trd = nullptr;   // non-null while a step is captured: its counter slot
+        hipGraphExec_t exec[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+        double dt[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        long long epoch[2][2] = {{-1, -1}, {-1, -1}};
+        int len[2][2] = {{0, 0}, {0, 0}};
+    } gr;
     long long epoch = 0;               // bumped by every call that may change buffers or settings
     long long tdev_next = -1;          // the step the device counter is valid for (-1: unknown)
     int graph = 16;                    // tuning "graph": steps per graph (even), 0 = no capture
     long long graph_steps = 0;         // steps run from graphs (tests, stats)
-    // Owner-computed assembly (tuning "own_assembly", hakai_own_plan.cpp own_plan): the persistent
-    // element kernel sums node forces in LDS in element order and stores Q (or a prefix partial plus
-    // the later contributions as rows) instead of the per-element fe array.
-    int own_assembly = 1;              // tuning value (1 = use when eligible; env HAKAI_OWN_ASSEMBLY)
-    long long own_built_g = -1;        // grid the lists were built for (-1 none, -2 mesh not suitable)
-    long long own_for_g0 = -1;         // persistent-kernel grid that build was for (a change rebuilds)
-    int own_band_rows = 0;             // tuning: row-band height of the banded schedule (0: planned)
-    int own_pass_batches = 0;          // tuning: batches per summing pass (0: 2 where they fit, else 1)
-    bool own_valid = false;            // d_own_q/d_own_rows hold the last element step's sums
-    int* d_own_off = nullptr;          // [nb+1] entry offsets per schedule position (super-batch starts)
-    int* d_own_seq = nullptr;          // [nb] batch at each schedule position (ascending within a block)
-    int* d_own_bstart = nullptr;       // [grid+1] first schedule position of each block
-    int own_banded = 0;                // the schedule walks row bands of a structured cross-section
-    long long own_round2 = 0;          // summing passes of the built lists that take a second entry per thread
-    int* d_own_list = nullptr;         // 4 ints per entry (+ one no-op entry at own_nop)
-    int own_nop = 0;
-    int own_slots = 0;                 // LDS running-sum slots the lists use (the kernel's dynamic LDS)
-    double* d_own_q = nullptr;         // [nN][3]
-    int* d_own_rp = nullptr;           // [nN+1]
-    double* d_own_rows = nullptr;      // [rows][3], numbered by super-batch
-    int* d_own_ridx = nullptr;         // rows of node n: own_ridx[own_rp[n] .. own_rp[n+1]), element order
-    double* d_own_dump = nullptr;      // [grid][8]
-    long long own_rows = 0, own_entries = 0;
-    long long own_steps = 0;           // element steps run with owner-computed assembly
-    int own_s = 2;                     // batches per super-batch of the built lists (2, or 1)
+    hkc::Own own;                      // owner-computed assembly (hakai_own.hpp)
     // multi-GPU
     hkc::Comm* comm = nullptr;
     // history output (hakai_history_enable; hakai_history.hpp has the hooks)
@@ -178,6 +153,19 @@ namespace hkc {
 inline const double* step_fext(const hakai_ctx* c) {
     return c->d_ftot ? c->d_ftot : (c->contact ? c->d_fext : nullptr);
 }
+// Grid of the persistent element kernel for this context (0: the one-batch-per-block kernel runs):
+// only with >= pipe_min batches per block.
+inline long long pipe_grid(const hakai_ctx* c) {
+    const long long nb = c->nEp / hk::kEPB;
+    const bool pipe = nb >= (long long)c->pipe_min * c->pipe_blocks && c->pipe_blocks > 0;
+    return pipe ? (nb < c->pipe_blocks ? nb : c->pipe_blocks) : 0;
+}
+// Kernel arguments for the context's buffers with disp = d_u[cur] (hakai_capi.cpp): the element
+// update without its owner-assembly part (own_elem_args), the nodal update without external force
+// and fused BCs, the boundary conditions of step t.
+hk::ElemArgs elem_args(const hakai_ctx* c, int cur);
+hk::NodalArgs nodal_args(const hakai_ctx* c, double d_time);
+hk::BCArgs bc_args(const hakai_ctx* c, double t, double d_time);
 void prof_begin(hakai_ctx* c, int kernel, EventPair* p);
 void prof_end(hakai_ctx* c, EventPair* p);
 void comm_destroy(hakai_ctx* c);
@@ -237,7 +225,8 @@ int contact_check(hakai_ctx* c);                          // buffer overflow che
 void contact_after_overflow(hakai_ctx* c, long long steps_since_reset);  // host state after a poisoned call
 bool contact_exchange_retry(hakai_ctx* c);                // that call overflowed a multi-GPU exchange,
                                                           // now grown: the step may run again
-void graph_invalidate(hakai_ctx* c);                      // drop captured step graphs (hakai_step)
+void graph_invalidate(hakai_ctx* c);                      // drop captured step graphs (hakai_step.cpp)
+void graph_free(hakai_ctx* c);
 bool contact_graph_ok(const hakai_ctx* c, double t);       // step t's contact work can be captured
 void contact_graph_advance(hakai_ctx* c, double t_last);   // host state after a cached graph's steps
 int contact_tuning(hakai_ctx* c, const char* key, long long value);  // "contact_*" tuning keys

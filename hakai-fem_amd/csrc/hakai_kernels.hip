@@ -19,8 +19,6 @@
 
 namespace hk {
 
-constexpr int kBlock = 256;
-constexpr int kEPB = kBlock / 8;     // elements per block
 constexpr int kLdsStride = 50;       // doubles per element slot: 8 nodes x (X,du) + pad (bank spread)
 // Owner-assembly force staging: [element][local node][3] with one pad double per element, so a
 // pass's entries reading the same local node of consecutive elements (lane stride 8) hit spread

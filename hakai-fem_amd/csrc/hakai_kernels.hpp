@@ -8,6 +8,9 @@
 
 namespace hk {
 
+constexpr int kBlock = 256;
+constexpr int kEPB = kBlock / 8;     // elements per block (a batch; the host pads meshes to whole batches)
+
 struct ElemArgs {
     const double* coord;   // 3nN reference position
     const double* u;       // disp  (after this step's update)

@@ -43,12 +43,6 @@
 using hkc::fail;
 using hkc::hip_fail;
 
-#define HIPCHK(x)                                           \
-    do {                                                    \
-        hipError_t _e = (x);                                \
-        if (_e != hipSuccess) return hip_fail(_e, #x);      \
-    } while (0)
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -300,8 +294,8 @@ static int loads_launch(hakai_ctx* c, double t, double d_time, const double* fc,
     a.fc = fc;
     a.mass = c->d_mass;
     a.coord = c->d_coord;
-    a.u = c->d_u[c->cur];
-    a.u_pre = c->d_u[1 - c->cur];
+    a.u = c->d_u[c->sv.cur];
+    a.u_pre = c->d_u[1 - c->sv.cur];
     a.conn = c->d_conn;
     a.flag = c->d_flag;
     a.ftot = c->d_ftot;
@@ -324,7 +318,7 @@ static int loads_launch(hakai_ctx* c, double t, double d_time, const double* fc,
 
 int loads_step(hakai_ctx* c, double t, double d_time, const double* fc) {
     if (!c->loads) return 0;
-    return loads_launch(c, t, d_time, fc, c->g_trd, c->stream, true, true);
+    return loads_launch(c, t, d_time, fc, c->gr.trd, c->stream, true, true);
 }
 
 // A probe: one part of the sum alone, at the current state. d_ftot is rewritten whole by every step

@@ -1,5 +1,5 @@
 // hakai_own_plan.hpp -- planner of owner-computed assembly: pure host code, no HIP, no context.
-// hakai_capi.cpp own_use fills OwnInput and uploads the plan; tools/own_plan_check.cpp replays it on
+// hakai_own.cpp own_prepare fills OwnInput and uploads the plan; tools/own_plan_check.cpp replays it on
 // the CPU (tests/test_own_plan.py).
 #pragma once
 #include <vector>

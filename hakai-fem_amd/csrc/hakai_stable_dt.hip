@@ -37,14 +37,10 @@
 #include "hakai_stable_dt.hpp"
 #include "hakai_stable_dt_elem.hpp"
 
+using hkc::dalloc;
+using hkc::dfree;
 using hkc::fail;
 using hkc::hip_fail;
-
-#define HIPCHK(x)                                           \
-    do {                                                    \
-        hipError_t _e = (x);                                \
-        if (_e != hipSuccess) return hip_fail(_e, #x);      \
-    } while (0)
 
 namespace {
 
@@ -236,18 +232,6 @@ __global__ __launch_bounds__(kThreads) void k_stable_dt_finish(const Part* part,
     if (tid == 0) *out = s[0];
 }
 
-template <class T>
-hipError_t dalloc(T** p, size_t n) {
-    *p = nullptr;
-    return hipMalloc((void**)p, (n ? n : 1) * sizeof(T));
-}
-
-template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
 }  // namespace
 
 namespace hkc {
@@ -314,7 +298,7 @@ extern "C" int hakai_stable_dt(hakai_ctx* c, double mass_scaling, double d_time,
                               hipMemcpyHostToDevice, st));
         Args a;
         a.coord = c->d_coord;
-        a.u = c->d_u[c->cur];
+        a.u = c->d_u[c->sv.cur];
         a.conn = c->d_conn;
         a.flag = c->d_flag;
         a.mat = c->d_mat;

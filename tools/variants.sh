@@ -14,7 +14,9 @@ done
 wait
 for o in build/variants/*.o; do
   name=$(basename $o .o)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o lib/variants/$name.so $o build/hakai_capi.o build/hakai_comm.o \
-    build/hakai_contact.o build/hakai_contact_xr.o build/hakai_contact_plan.o build/hakai_own_plan.o build/hakai_host.o build/hakai_vtk.o -L/opt/rocm/lib -lrccl -lamdhip64 -pthread
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o lib/variants/$name.so $o build/hakai_capi.o build/hakai_step.o build/hakai_own.o build/hakai_comm.o \
+    build/hakai_contact.o build/hakai_contact_xr.o build/hakai_contact_plan.o build/hakai_own_plan.o build/hakai_history.o \
+    build/hakai_stable_dt.o build/hakai_loads.o build/hakai_loads_plan.o build/hakai_walls_plan.o build/hakai_host.o \
+    build/hakai_history_host.o build/hakai_stable_dt_host.o build/hakai_vtk.o -L/opt/rocm/lib -lrccl -lamdhip64 -pthread
 done
 ls -la lib/variants
