@@ -233,6 +233,9 @@ hk::ElemArgs elem_args(const hakai_ctx* c, int cur) {
     ea.conn = c->d_conn;
     ea.flag = c->d_flag;
     ea.mat = c->d_mat;
+    // one material: every entry of d_mat is 0 (hakai_upload_model), so the kernels read d_mat[0]
+    // for every element instead of streaming the array
+    ea.mat_stride = c->nmat == 1 ? 0u : 4u;
     ea.mats = c->d_mats;
     ea.stress = c->d_stress;
     ea.strain = c->d_strain;

@@ -92,7 +92,7 @@ __device__ __forceinline__ void load_stage_a(const ElemArgs& a, long long e, int
     const unsigned ue = (unsigned)e;
     in.fl = *at32(a.flag, 4u * ue);
     in.n = *at32(a.conn, 32u * ue + 4u * (unsigned)k);
-    in.mt = *at32(a.mat, 4u * ue);
+    in.mt = *at32(a.mat, a.mat_stride * ue);  // (stride 0: one material, every lane reads mat[0] = 0)
     const int kn = EXACT ? k : ref_of_sign(k);  // the node whose force lane k ends up with
     in.fb = (int)(24 * e + 3 * kn);
 }
@@ -894,11 +894,41 @@ __device__ __forceinline__ int4 own_load(const ElemArgs& a, long long b) {
     return en;
 }
 
+// Template form (ElemArgs::own_hdr, hakai_own_plan.hpp): the super-batch's header is block-uniform
+// and is loaded one stage before its entries (with load_stage_a of the batch after), so the entry
+// load, which needs the header's offset and count, keeps its place one batch ahead and waits for
+// nothing that is still far away. The entries are shared between super-batches and stay in L2.
+//
+// The header is read through the constant address space, i.e. with a scalar load into SGPRs: the
+// headers are written by the host before the launch and by nothing else, the index is the same for
+// the whole block, and a vector load would hold four VGPRs per header in flight (three headers are
+// live: the kernel has none to spare in reference-order mode) and count against vmcnt.
+__device__ __forceinline__ int4 own_hdr_load(const ElemArgs& a, long long b) {
+    typedef const int __attribute__((address_space(4))) * ConstInt;
+    const ConstInt p = (ConstInt)(unsigned long long)(a.own_hdr + b);
+    return make_int4(p[0], p[1], p[2], p[3]);  // (one s_load_dwordx4)
+}
+
+__device__ __forceinline__ int4 own_load_tpl(const ElemArgs& a, int4 h) {
+    const int cnt = own_hdr_count(h.y);
+    int4 en = a.own_list[(int)threadIdx.x < cnt ? h.x + (int)threadIdx.x : a.own_nop];
+    en.y |= (cnt > kBlock) ? kOwnRound2 : 0;
+    return en;
+}
+
 __device__ __forceinline__ int own_lane(int4 en, int j) { return own_lane(en.y, en.z, en.w, j); }
 
-__device__ __forceinline__ void own_entry(const ElemArgs& a, int4 en, const double* s_fe, double* s_part) {
+// h: the super-batch's header (TPL only): targets are relative to its bases, an ACC entry's slot is
+// node mod own_slots (own_tpl_slot)
+template <bool TPL>
+__device__ __forceinline__ void own_entry(const ElemArgs& a, int4 en, int4 h, const double* s_fe, double* s_part) {
 #pragma clang fp contract(off)
-    const int slot = own_slot(en.y), flags = own_flags(en.y), n = own_n(en.y);
+    const int flags = own_flags(en.y), n = own_n(en.y);
+    int slot = own_slot(en.y);
+    if (TPL) {
+        if (!(flags & (kOwnExp | kOwnNop))) slot = own_tpl_slot(en.x, own_hdr_sofs(h.y), a.own_slots);
+        en.x += (flags & kOwnExp) ? h.w : h.z;
+    }
     double* dump = a.own_dump + 8 * (long long)blockIdx.x;
     double v[3];
     if (flags & (kOwnExp | kOwnNop)) {  // EXP: up to kOwnExpRows contributions -> rows target + j * stride
@@ -948,7 +978,8 @@ struct PassClock {
 // One summing pass: the prefetched entry of this thread, then -- only for a super-batch with more
 // than kBlock entries (wide cross-sections) -- a second one, loaded here (that pass waits for it).
 // Entries of one pass touch distinct LDS slots, so the two rounds need no barrier between them.
-__device__ __forceinline__ void own_pass(const ElemArgs& a, int4 en, long long sb, const double* s_fe,
+template <bool TPL>
+__device__ __forceinline__ void own_pass(const ElemArgs& a, int4 en, int4 h, long long sb, const double* s_fe,
                                          double* s_part HK_DIAG_ARG) {
 #ifdef HK_DIAG_WAVE
     const long long t0 = clock64();
@@ -959,12 +990,19 @@ __device__ __forceinline__ void own_pass(const ElemArgs& a, int4 en, long long s
 #endif
     // a wave whose threads hold no entry of this round skips it (wave-uniform: no-op entries only
     // store to the dump line; C3 -0.8 to -1.0 %, C4 -1.0 %, profiles/r05_pass_skip_empty_waves_ab.log)
-    const int o0 = a.own_off[sb], o1 = a.own_off[sb + 1];
-    if (o0 + (int)(threadIdx.x & ~63u) < o1) own_entry(a, en, s_fe, s_part);
+    int o0, o1;  // the super-batch's entries (TPL: in the template store, from the header)
+    if (TPL) {
+        o0 = h.x;
+        o1 = h.x + own_hdr_count(h.y);
+    } else {
+        o0 = a.own_off[sb];
+        o1 = a.own_off[sb + 1];
+    }
+    if (o0 + (int)(threadIdx.x & ~63u) < o1) own_entry<TPL>(a, en, h, s_fe, s_part);
     if (en.y & kOwnRound2) {  // block-uniform
         const int idx = o0 + kBlock + (int)threadIdx.x;
         if (o0 + kBlock + (int)(threadIdx.x & ~63u) < o1)
-            own_entry(a, a.own_list[idx < o1 ? idx : a.own_nop], s_fe, s_part);
+            own_entry<TPL>(a, a.own_list[idx < o1 ? idx : a.own_nop], h, s_fe, s_part);
     }
 #ifdef HK_DIAG_WAVE
     const long long t2 = clock64();
@@ -978,7 +1016,9 @@ __device__ __forceinline__ void own_pass(const ElemArgs& a, int4 en, long long s
 // issuing the loads of batch b+2 (connectivity, flags) and b+1 (node gathers, Gauss-point state)
 // before computing batch b, so HBM latency hides under the FP64 work even at 2 waves per SIMD.
 // Material tables are staged in LDS (segment searches hit LDS, not L2).
-template <bool DO_DELETE, bool STORE_TRIAX, bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS = 0>
+// TPL: the owner-assembly lists are in template form (compile-time, so neither form pays a branch).
+template <bool DO_DELETE, bool STORE_TRIAX, bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS = 0,
+          bool TPL = false>
 __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
     constexpr bool OWN = OS > 0;                 // owner-computed assembly, OS batches per super-batch
     constexpr int kOwnFe = OS * kEPB * kFeStride;  // staged forces per pass (doubles)
@@ -1050,10 +1090,19 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
     // the schedule position of its first batch)
     constexpr int S = OS > 0 ? OS : 1;
     auto sb_of = [&](long long i) { return pos_of((i < count ? i : count - 1) / S * S); };
-    if (OWN) ent_cur = own_load(a, sb_of(0));
+    // (TPL: headers of the super-batches of iterations i, i + 1, i + 2)
+    int4 hdr_cur = {0, 0, 0, 0}, hdr_nxt = {0, 0, 0, 0}, hdr_nn = {0, 0, 0, 0};
+    if (OWN && TPL) {
+        hdr_cur = own_hdr_load(a, sb_of(0));
+        hdr_nxt = own_hdr_load(a, sb_of(1));
+        ent_cur = own_load_tpl(a, hdr_cur);
+    } else if (OWN) {
+        ent_cur = own_load(a, sb_of(0));
+    }
     for (long long i = 0; i < count; ++i) {
         ElemIn nn;
         load_stage_a<EXACT>(a, elem_of(i + 2), k, nn);
+        if (OWN && TPL) hdr_nn = own_hdr_load(a, sb_of(i + 2));
         // (reference-order mode: its longer arithmetic holds more registers, so nothing of the
         // current batch's nodes or Gauss points is loaded a batch ahead -- only connectivity and
         // flags, two batches ahead. The node gathers are issued at the start of the batch and
@@ -1062,7 +1111,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
         // issuing this batch's node and/or Gauss-point loads at the end of the previous batch (before
         // its summing pass) spills and measured 1.18-1.28 against 1.10 ms, profiles/r03_exact_early_loads_ab.log.)
         if (!EXACT) load_stage_b<ANY_PLASTIC, NT>(a, elem_of(i + 1), k, nxt);
-        if (OWN) ent_nxt = own_load(a, sb_of(i + 1));
+        if (OWN) ent_nxt = TPL ? own_load_tpl(a, hdr_nxt) : own_load(a, sb_of(i + 1));
         double* sfe = s_fe + ((i / S) & 1) * kOwnFe + (i % S) * (kEPB * kFeStride);
         if (EXACT) {
 #ifdef HK_DIAG_PHASE
@@ -1080,8 +1129,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
             // block-uniform branch; the compiler's load accounting is the same on both sides
             // (checked in the ISA: identical vmcnt waits with or without balancing stores)
             if ((i + 1) % S == 0 || i + 1 == count)
-                own_pass(a, ent_cur, sb_of(i), s_fe + ((i / S) & 1) * kOwnFe, s_part HK_DIAG_PASS);
+                own_pass<TPL>(a, ent_cur, hdr_cur, sb_of(i), s_fe + ((i / S) & 1) * kOwnFe, s_part HK_DIAG_PASS);
             ent_cur = ent_nxt;
+            if (TPL) {
+                hdr_cur = hdr_nxt;
+                hdr_nxt = hdr_nn;
+            }
         }
         cur = nxt;
         nxt = nn;
@@ -1137,37 +1190,41 @@ static void launch_element_w(const ElemArgs& a, bool do_delete, bool store_triax
     }
 }
 
-template <bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS>
+template <bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS, bool TPL = false>
 static void launch_pipe(const ElemArgs& a, bool do_delete, bool store_triax, unsigned grid, hipStream_t s) {
     const size_t dyn = (OS > 0 ? 24 * (size_t)a.own_slots : 0) + (LDS_MATS ? sizeof(DevMat) * (size_t)a.nmat : 0);
     if (do_delete) {
         if (store_triax)
-            hipLaunchKernelGGL((k_element_pipe<true, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<true, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
         else
-            hipLaunchKernelGGL((k_element_pipe<true, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<true, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
     } else {
         if (store_triax)
-            hipLaunchKernelGGL((k_element_pipe<false, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<false, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
         else
-            hipLaunchKernelGGL((k_element_pipe<false, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<false, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
     }
 }
 
-template <bool ANY_PLASTIC, bool LDS_MATS, bool EXACT, int OS>
+template <bool ANY_PLASTIC, bool LDS_MATS, bool EXACT, int OS, bool TPL = false>
 static void launch_pipe_nt(const ElemArgs& a, bool do_delete, bool store_triax, unsigned grid, hipStream_t s) {
     if (a.gp_nt)
-        launch_pipe<ANY_PLASTIC, LDS_MATS, 3, EXACT, OS>(a, do_delete, store_triax, grid, s);
+        launch_pipe<ANY_PLASTIC, LDS_MATS, 3, EXACT, OS, TPL>(a, do_delete, store_triax, grid, s);
     else
-        launch_pipe<ANY_PLASTIC, LDS_MATS, 0, EXACT, OS>(a, do_delete, store_triax, grid, s);
+        launch_pipe<ANY_PLASTIC, LDS_MATS, 0, EXACT, OS, TPL>(a, do_delete, store_triax, grid, s);
 }
 
 template <bool ANY_PLASTIC, bool LDS_MATS, bool EXACT>
 static void launch_pipe_os(const ElemArgs& a, bool do_delete, bool store_triax, unsigned grid, hipStream_t s) {
-    if (a.own == 1)
+    if (a.own == 1 && a.own_hdr)
+        launch_pipe_nt<ANY_PLASTIC, true, EXACT, 1, true>(a, do_delete, store_triax, grid, s);
+    else if (a.own == 2 && a.own_hdr)
+        launch_pipe_nt<ANY_PLASTIC, true, EXACT, 2, true>(a, do_delete, store_triax, grid, s);
+    else if (a.own == 1)
         launch_pipe_nt<ANY_PLASTIC, true, EXACT, 1>(a, do_delete, store_triax, grid, s);
     else if (a.own == 2)
         launch_pipe_nt<ANY_PLASTIC, true, EXACT, 2>(a, do_delete, store_triax, grid, s);
@@ -1193,7 +1250,7 @@ hipError_t launch_element(const ElemArgs& a, bool do_delete, bool store_triax, h
     const long long nb = a.nEp / kEPB;
     if (nb <= 0) return hipSuccess;
     if (a.own) {  // owner-computed assembly: persistent kernel only (own_plan sized its lists for it)
-        if (a.own > 2 || a.vol || a.pipe_blocks <= 0 || a.nmat > kMaxLdsMats || !a.own_off || !a.own_list ||
+        if (a.own > 2 || a.vol || a.pipe_blocks <= 0 || a.nmat > kMaxLdsMats || !(a.own_off || a.own_hdr) || !a.own_list ||
             !a.own_seq || !a.own_bstart || !a.own_q || !a.own_dump || a.own_slots < 1 ||
             a.own_slots > own_slot_cap(a.exact != 0, a.own, a.nmat))
             return hipErrorInvalidValue;

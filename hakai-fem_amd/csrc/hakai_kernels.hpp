@@ -18,6 +18,8 @@ struct ElemArgs {
     const int* conn;       // 8nE, 0-based
     int* flag;             // nE: 1 active, 2 deleted in the previous step (fe still live), 0 deleted
     const int* mat;        // nE, 0-based
+    unsigned mat_stride;   // bytes between elements' entries of mat: 4, or 0 for a one-material model
+                           // (every lane then reads mat[0], which is 0)
     const DevMat* mats;
     double* stress;        // SoA [6][ld]
     double* strain;        // SoA [6][ld]
@@ -58,8 +60,11 @@ struct ElemArgs {
     const int* own_bstart;  // [own_bstart[lb], own_bstart[lb+1]) (batches ascending within a block)
     const int* own_off;     // [nb+1] entry offsets, indexed by the position of a super-batch's first batch
     const int4* own_list;
+    // Template form (hakai_own_plan.hpp) when own_hdr is set: [nb] headers indexed like own_off,
+    // own_list is the template store and own_off is not read.
+    const int4* own_hdr;
     int own_nop;            // index of a no-op entry (list padding)
-    int own_slots;          // LDS running-sum slots the lists use (1..1024)
+    int own_slots;          // LDS running-sum slots the lists use (template form: the modulus P)
     double* own_q;          // [nN][3]
     double* own_rows;       // [rows][3]
     double* own_dump;       // [grid][8] target of the no-op entries' stores

@@ -36,8 +36,10 @@ static bool own_upload(hakai_ctx* c, const hk::OwnSched& sc, const hk::OwnPlan& 
     const long long nN = c->nN, G = (long long)sc.bstart.size() - 1;
     std::vector<int> bst(sc.bstart.begin(), sc.bstart.end());
     hipStream_t s = c->stream;
-    if (l.d_off.upload(pl.off, s) || l.d_seq.upload(sc.seq, s) || l.d_bstart.upload(bst, s) ||
-        l.d_list.upload(pl.list, s) || l.d_rp.upload(pl.rp, s) || l.d_ridx.upload(pl.ridx, s) ||
+    // the entries: the template store and the headers, or the plain list and its offsets
+    if ((pl.tpl ? l.d_hdr.upload(pl.hdr, s) || l.d_list.upload(pl.tlist, s)
+                : l.d_off.upload(pl.off, s) || l.d_list.upload(pl.list, s)) ||
+        l.d_seq.upload(sc.seq, s) || l.d_bstart.upload(bst, s) || l.d_rp.upload(pl.rp, s) || l.d_ridx.upload(pl.ridx, s) ||
         l.d_q.alloc(3 * (size_t)nN) || l.d_rows.alloc(3 * (size_t)std::max(pl.rows, 1LL)) ||
         l.d_dump.alloc(8 * (size_t)G) ||
         hipMemsetAsync(l.d_q, 0, 3 * (size_t)nN * sizeof(double), s) ||  // nodes without elements
@@ -45,8 +47,10 @@ static bool own_upload(hakai_ctx* c, const hk::OwnSched& sc, const hk::OwnPlan& 
         own_free(c);
         return false;
     }
-    l.nop = (int)pl.ne;
-    l.slots = pl.max_slots;
+    l.nop = (int)(pl.tpl ? pl.stored : pl.ne);
+    l.slots = pl.tpl ? pl.P : pl.max_slots;
+    l.stored = pl.tpl ? pl.stored : pl.ne;
+    l.templates = pl.tpl ? pl.templates : 0;
     l.rows = pl.rows;
     l.entries = pl.ne;
     l.built_g = G;
@@ -102,7 +106,8 @@ bool own_prepare(hakai_ctx* c) {
         const hk::OwnInput in{c->nE, c->nN, c->nEp, c->h_conn, c->h_ptr, c->h_inc0, c->max_inc,
                               c->own.band_rows, c->own.pass_batches, comm_dn_nodes(c),
                               {hk::own_slot_cap(c->elem_exact != 0, 1, c->nmat),
-                               hk::own_slot_cap(c->elem_exact != 0, 2, c->nmat)}};
+                               hk::own_slot_cap(c->elem_exact != 0, 2, c->nmat)},
+                              c->own.templates};
         hk::OwnSched sc;
         hk::OwnPlan pl;
         if (!(hk::own_choose(in, G0, sc, pl) && own_upload(c, sc, pl))) {
@@ -122,6 +127,7 @@ void own_elem_args(const hakai_ctx* c, hk::ElemArgs& ea) {
     ea.own_bstart = l.d_bstart;
     ea.own_off = l.d_off;
     ea.own_list = reinterpret_cast<const int4*>(l.d_list.get());
+    ea.own_hdr = reinterpret_cast<const int4*>(l.d_hdr.get());  // null: plain form
     ea.own_nop = l.nop;
     ea.own_slots = l.slots;
     ea.own_q = l.d_q;
@@ -140,6 +146,12 @@ int own_tuning(hakai_ctx* c, const char* key, long long value) {
         if (value < 0 || value > 2) return fail(HAKAI_ERR_ARG, "own_pass_batches must be 0, 1 or 2");
         if (o.pass_batches != (int)value) o.for_g0 = -1;  // re-plan at the next step
         o.pass_batches = (int)value;
+        return 0;
+    }
+    if (!std::strcmp(key, "own_templates")) {  // template form of the entry lists where the plan offers one
+        if (value < 0 || value > 1) return fail(HAKAI_ERR_ARG, "own_templates must be 0 or 1");
+        if (o.templates != (int)value) o.for_g0 = -1;  // re-plan at the next step
+        o.templates = (int)value;
         return 0;
     }
     if (!std::strcmp(key, "own_band_rows")) {  // row-band height of the banded owner schedule (0: planned)
@@ -173,6 +185,8 @@ int own_stat(const hakai_ctx* c, const char* key, int64_t* value) {
     if (!std::strcmp(key, "own_steps")) *value = c->own.steps;
     else if (!std::strcmp(key, "own_rows")) *value = built ? l.rows : -1;
     else if (!std::strcmp(key, "own_entries")) *value = built ? l.entries : -1;
+    else if (!std::strcmp(key, "own_entries_stored")) *value = built ? l.stored : -1;
+    else if (!std::strcmp(key, "own_templates")) *value = built ? l.templates : 0;
     else if (!std::strcmp(key, "own_superbatch")) *value = built ? l.s : 0;
     else if (!std::strcmp(key, "own_round2")) *value = built ? l.round2 : 0;
     else if (!std::strcmp(key, "own_slots")) *value = built ? l.slots : 0;

@@ -15,6 +15,7 @@ struct Own {
     int assembly = 1;        // tuning value (1 = use when eligible; env HAKAI_OWN_ASSEMBLY)
     int band_rows = 0;       // tuning: row-band height of the banded schedule (0: planned)
     int pass_batches = 0;    // tuning: batches per summing pass (0: 2 where they fit, else 1)
+    int templates = 1;       // tuning: 1 = template form of the entry lists when the plan offers one
     long long for_g0 = -1;   // persistent-kernel grid the lists were built for (a change rebuilds)
     long long steps = 0;     // element steps run with owner-computed assembly
     // The uploaded plan; own_free drops it whole.
@@ -25,7 +26,10 @@ struct Own {
         DevBuf<int> d_bstart;      // [grid+1] first schedule position of each block
         int banded = 0;            // the schedule walks row bands of a structured cross-section
         long long round2 = 0;      // summing passes that take a second entry per thread
-        DevBuf<int> d_list;        // 4 ints per entry (+ one no-op entry at nop)
+        DevBuf<int> d_list;        // 4 ints per entry (+ one no-op entry at nop); template form: the store
+        DevBuf<int> d_hdr;         // template form: [nb] 16-byte headers, indexed like d_off (then not uploaded)
+        long long stored = 0;      // entries in d_list without the no-op entry (= entries in plain form)
+        long long templates = 0;   // distinct passes stored (0: plain form)
         int nop = 0;
         int slots = 0;             // LDS running-sum slots the lists use (the kernel's dynamic LDS)
         DevBuf<double> d_q;        // [nN][3]

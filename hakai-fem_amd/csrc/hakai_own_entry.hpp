@@ -53,4 +53,28 @@ HK_HD int own_lane(int y, int z, int w, int j) {
     return j < 7 ? (int)((lo >> (9 * j)) & 511) : (int)(((unsigned)y >> 18) & 511);  // bits 18-26
 }
 
+// Template form (hakai_own_plan.hpp): the entries of a super-batch are stored with relative targets
+// (ACC: node - tbase, EXP: row - rbase; an ACC entry's slot field is 0, its slot is node mod P) and
+// shared between super-batches whose relative lists are equal. One 16-byte header per super-batch:
+//   x = offset of its entries in the template store, y = entry count | (tbase mod P) << 16,
+//   z = tbase, w = rbase.
+constexpr int kOwnTplMinEntries = 1 << 16;  // shorter plain lists (1 MiB) sit in L2 whole: the form is kept whatever it stores
+
+HK_HD void own_pack_hdr(int toff, int count, int sofs, int tbase, int rbase, int h[4]) {
+    h[0] = toff;
+    h[1] = (int)((unsigned)count | (unsigned)sofs << 16);
+    h[2] = tbase;
+    h[3] = rbase;
+}
+HK_HD int own_hdr_count(int y) { return y & 0xffff; }
+HK_HD int own_hdr_sofs(int y) { return (int)((unsigned)y >> 16); }
+// node mod P of a relative ACC target: rel < 2 P and sofs = tbase mod P < P, so two conditional
+// subtractions (the unsigned minimum takes the difference exactly when it does not wrap)
+HK_HD int own_tpl_slot(int rel, int sofs, int P) {
+    unsigned s = (unsigned)rel + (unsigned)sofs, t = s - (unsigned)P;
+    s = t < s ? t : s;
+    t = s - (unsigned)P;
+    return (int)(t < s ? t : s);
+}
+
 }  // namespace hk

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <unordered_map>
 #include <utility>
 
 #include "hakai_own_entry.hpp"
@@ -152,6 +154,20 @@ static bool own_banded(const OwnInput& in, long long G, const std::vector<int>& 
     return true;
 }
 
+int OwnTplStore::add(const int* rel, int count) {
+    unsigned long long h = 14695981039346656037ull ^ (unsigned)count;  // FNV-1a over the whole list
+    for (int q = 0; q < 4 * count; ++q) h = (h ^ (unsigned)rel[q]) * 1099511628211ull;
+    std::vector<std::pair<int, int>>& cands = seen[h];
+    for (const std::pair<int, int>& c : cands)  // compared on a hit: equal hashes do not prove equal lists
+        if (c.second == count && (count == 0 || !std::memcmp(&tl[4 * (size_t)c.first], rel, sizeof(int) * 4 * (size_t)count)))
+            return c.first;
+    const int toff = (int)(tl.size() / 4);
+    tl.insert(tl.end(), rel, rel + 4 * (size_t)count);
+    cands.emplace_back(toff, count);
+    ++distinct;
+    return toff;
+}
+
 static bool own_plan(const OwnInput& in, const OwnSched& sc, int S, int slot_cap, OwnPlan& pl) {
     const int epb = sc.epb, bs = 8 * epb;  // elements per batch, threads per block
     const long long nb = in.nEp / epb, nN = in.nN;
@@ -175,7 +191,7 @@ static bool own_plan(const OwnInput& in, const OwnSched& sc, int S, int slot_cap
     std::vector<int> rp(nN + 1, 0);
     long long rows = 0;
     // open-sum intervals per block in super-batch units: (first, last, entry refs to patch the slot)
-    struct Seg { long long s0, s1; std::vector<std::pair<long long, int>> refs; };
+    struct Seg { long long s0, s1; int node; std::vector<std::pair<long long, int>> refs; };
     std::vector<std::vector<Seg>> segs(G);
     auto batch_of = [&](int j) { return (long long)(in.inc0[j] / 8) / epb; };
     // LDS lane of incidence j within its super-batch: (position - super-batch position) * epb +
@@ -204,6 +220,7 @@ static bool own_plan(const OwnInput& in, const OwnSched& sc, int S, int slot_cap
         int j = j0;
         Seg sg;
         sg.s0 = -1;
+        sg.node = (int)n;
         while (j < j1 && block_of[batch_of(j)] == hb) {  // the head segment, super-batch by super-batch
             const long long sb = sb_pos[batch_of(j)];
             Ent en{(int)n, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
@@ -336,6 +353,88 @@ static bool own_plan(const OwnInput& in, const OwnSched& sc, int S, int slot_cap
     pl.rows = rows;
     pl.ne = ne;
     pl.max_slots = max_slots;
+    // ---- template form (hakai_own_plan.hpp): the same passes with relative targets, each distinct
+    // one stored once, and slot = node mod P
+    pl.tpl = false;
+    pl.P = 0;
+    pl.hdr.clear();
+    pl.tlist.clear();
+    pl.stored = pl.templates = pl.passes = 0;
+    if (!in.templates) return true;
+    // bases, and the widest relative ACC target (2 P must exceed it: own_tpl_slot)
+    std::vector<int> tbase(nb, 0), rbase(nb, 0);
+    long long max_rel = 0;
+    for (long long b = 0; b < nb; ++b) {
+        long long t0 = -1, t1 = -1, r0 = -1;
+        for (const Ent& en : per[b]) {
+            if (en.flags & kOwnExp) {
+                r0 = r0 < 0 ? en.target : std::min<long long>(r0, en.target);
+            } else {
+                t0 = t0 < 0 ? en.target : std::min<long long>(t0, en.target);
+                t1 = std::max<long long>(t1, en.target);
+            }
+        }
+        tbase[b] = (int)std::max(t0, 0LL);
+        rbase[b] = (int)std::max(r0, 0LL);
+        max_rel = std::max(max_rel, t1 - t0);
+    }
+    // P is valid when, in every block, no two sums open over overlapping super-batch intervals
+    // share node mod P (segs[lb] is sorted by s0: a sum still holding the slot shows as s1 >= s0)
+    std::vector<long long> until;
+    auto valid = [&](int P) {
+        for (long long lb = 0; lb < G; ++lb) {
+            until.assign((size_t)P, -1);
+            for (const Seg& sg : segs[lb]) {
+                long long& u = until[(size_t)(sg.node % P)];
+                if (u >= sg.s0) return false;
+                u = sg.s1;
+            }
+        }
+        return true;
+    };
+    int P = 0;
+    {
+        const long long least = std::max<long long>(max_slots, max_rel / 2 + 1);  // rel < 2 P
+        long long p2 = 1;
+        while (p2 < least) p2 *= 2;
+        for (; p2 <= slot_cap && !P; p2 *= 2)
+            if (valid((int)p2)) P = (int)p2;
+        // (no power of two fits the reference-order kernel's 874 slots on a 20x20 section, whose
+        // open sums span more than 512 ids; and a modulus near a multiple of the node-layer stride
+        // folds two open layers onto each other, so the others are tried from the largest down --
+        // a modulus that fails does so within the first blocks)
+        for (long long p = slot_cap; p >= least && !P; --p)
+            if (valid((int)p)) P = (int)p;
+    }
+    if (!P) return true;  // plain form only
+    OwnTplStore store(pl.tlist);
+    std::vector<int> rel;
+    pl.hdr.assign(4 * (size_t)nb, 0);
+    for (long long lb = 0; lb < G; ++lb)
+        for (long long b = sc.bstart[lb]; b < sc.bstart[lb + 1]; b += S) {  // the super-batches' first positions
+            ++pl.passes;
+            const int cnt = (int)per[b].size();
+            rel.resize(4 * (size_t)cnt);
+            for (int i = 0; i < cnt; ++i) {
+                const Ent& en = per[b][(size_t)i];
+                const bool ex = (en.flags & kOwnExp) != 0;
+                own_pack(en.target - (ex ? rbase[b] : tbase[b]), ex ? en.slot : 0, en.flags, en.n, en.lanes, &rel[4 * (size_t)i]);
+            }
+            own_pack_hdr(store.add(rel.data(), cnt), cnt, tbase[b] % P, tbase[b], rbase[b], &pl.hdr[4 * (size_t)b]);
+        }
+    pl.templates = store.distinct;
+    std::vector<int>& tl = pl.tlist;
+    pl.stored = (long long)(tl.size() / 4);
+    tl.resize(tl.size() + 4);
+    own_pack(0, 0, kOwnNop, 0, no_lanes, &tl[4 * (size_t)pl.stored]);
+    if (pl.ne >= kOwnTplMinEntries && 2 * (pl.stored + pl.passes) > pl.ne) {  // the store would not halve the list
+        pl.hdr.clear();
+        pl.tlist.clear();
+        pl.stored = pl.templates = 0;
+        return true;
+    }
+    pl.P = P;
+    pl.tpl = true;
     return true;
 }
 

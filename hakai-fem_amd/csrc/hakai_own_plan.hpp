@@ -2,6 +2,8 @@
 // hakai_own.cpp own_prepare fills OwnInput and uploads the plan; tools/own_plan_check.cpp replays it on
 // the CPU (tests/test_own_plan.py).
 #pragma once
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace hk {
@@ -22,6 +24,19 @@ namespace hk {
 // entries), one or two per thread (format: hakai_own_entry.hpp, kernel: hakai_kernels.hip
 // own_pass). Slots are allocated per block over the super-batches a sum is open; a schedule needing
 // more than own_slot_cap open sums in one block, or a node with > 8 incidences, does not use the mode.
+//
+// Template form. On a lattice mesh two super-batches that meet the section's layer pattern at the
+// same phase hold the same flags, counts and lanes and differ only by a constant added to their
+// node targets and to their row targets. So each super-batch gets a 16-B header {template offset,
+// entry count and slot offset, tbase, rbase} (own_pack_hdr), and its entries are stored with targets
+// relative to tbase (ACC: the smallest node of the pass) or rbase (EXP: its smallest row); identical
+// relative lists are stored once and stay in L2. The allocator's slots would break the repetition,
+// so the slot is computed: slot = node mod P, which the kernel forms without a division as
+// rel + tbase mod P (the header's slot offset), less P while that is >= P, at most twice. The planner
+// proves P: in a block no two sums open over overlapping super-batch intervals share node mod P, and
+// every relative ACC target is < 2 P. Candidates are the powers of two from the plain plan's slot count up
+// to slot_cap, then the other values from slot_cap down. Without a valid P (row bands, shuffled numbering), or when a
+// list of kOwnTplMinEntries or more would not shrink to half, the plan keeps the plain form only.
 //
 // Schedules (own_choose picks the cheapest that fits):
 //  * contiguous: block lb holds batches [lb*nb/G, (lb+1)*nb/G) -- a slender section (C3) keeps all
@@ -45,9 +60,29 @@ struct OwnPlan {
     long long rows = 0, ne = 0;
     int max_slots = 1;
     long long round2 = 0;  // summing passes with more than one entry per thread
-    // per-step bytes the lists add beyond the element/nodal kernels' own (entries read, rows
-    // written and read back, row indices): what own_choose compares between schedules
-    double cost() const { return 16.0 * (double)ne + 52.0 * (double)rows; }
+    // Template form (own_templates below): an equivalent second representation of off/list, present
+    // when tpl is set. The kernel then reads hdr and tlist and never off and list.
+    bool tpl = false;
+    int P = 0;               // running-sum slots of the template form: slot = node mod P
+    std::vector<int> hdr;    // [4 nb] per schedule position (super-batch starts): own_pack_hdr
+    std::vector<int> tlist;  // 4 ints per stored entry, targets relative, + the no-op entry last
+    long long stored = 0;    // entries in tlist (without the no-op entry)
+    long long templates = 0; // distinct passes stored
+    long long passes = 0;    // super-batches (headers read per step)
+    // per-step bytes the lists add beyond the element/nodal kernels' own (entries read -- in template
+    // form the stored entries, which stay in L2, and one header per pass --, rows written and read
+    // back, row indices): what own_choose compares between schedules
+    double cost() const { return 16.0 * (double)(tpl ? stored + passes : ne) + 52.0 * (double)rows; }
+};
+
+// The template store: relative passes (4 ints per entry), each distinct one kept once.
+struct OwnTplStore {
+    explicit OwnTplStore(std::vector<int>& store) : tl(store) {}
+    int add(const int* rel, int count);  // offset (in entries) of the stored copy of this pass
+    long long distinct = 0;
+private:
+    std::vector<int>& tl;
+    std::unordered_map<unsigned long long, std::vector<std::pair<int, int>>> seen;  // hash -> (offset, count)
 };
 
 // Everything the planner reads.
@@ -61,6 +96,7 @@ struct OwnInput {
     int pass_batches;              // tuning own_pass_batches (0: 2 where they fit, else 1)
     const std::vector<int>* all_rows;  // nodes whose contributions must all be rows, or null
     int slot_cap[2];               // own_slot_cap for S = 1, 2
+    int templates = 1;             // tuning own_templates: derive the template form where the plan admits one
 };
 
 // Candidate schedules, cheapest plan wins (OwnPlan::cost): contiguous at the persistent grid G0,

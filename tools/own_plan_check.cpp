@@ -17,7 +17,13 @@
 // Prints one JSON line: {"ok": ..., "planned": ..., "epb", "grid", "superbatch", "banded", "rows",
 // "entries", "slots", "mismatch", "digest"} and exits 0 when the replay matches (or no plan fits:
 // planned false). digest: 64-bit FNV-1a over the plan (epb, S, seq, bstart, off, list, rp, ridx).
-// --selftest packs entries at the field extremes and reads them back (exit 1 on a mismatch).
+// Where the plan offers the template form (hakai_own_plan.hpp: headers, relative targets, slot =
+// node mod P) the replay runs a second time in that form, exactly as the kernel reads it, and both
+// must match; "template_form" (0 or 1), "templates" (distinct passes), "entries_stored", "passes"
+// and "template_slots" (P) report it.
+// --selftest packs entries and headers at the field extremes and reads them back, checks node mod P
+// by conditional subtraction, and that the template store keeps two passes apart that differ in one
+// lane id (exit 1 on a mismatch).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -68,6 +74,39 @@ int selftest() {
                         bad += ok ? 0 : 1;
                         ++n_checked;
                     }
+    // header fields at their extremes, and node mod P without a division
+    for (int count : {0, 1, 512})
+        for (int sofs : {0, 1, hk::kOwnSlotsMax - 1}) {
+            int h[4];
+            hk::own_pack_hdr(INT_MAX, count, sofs, INT_MAX - 1, 7, h);
+            bad += (h[0] == INT_MAX && hk::own_hdr_count(h[1]) == count && hk::own_hdr_sofs(h[1]) == sofs &&
+                    h[2] == INT_MAX - 1 && h[3] == 7) ? 0 : 1;
+            ++n_checked;
+        }
+    for (int P : {1, 2, 874, 1024, hk::kOwnSlotsMax})
+        for (int tbase : {0, 1, P - 1, P, 12345, INT_MAX - hk::kOwnSlotsMax})
+            for (int rel : {0, 1, P / 2, P - 1, P, 2 * P - 1}) {
+                bad += hk::own_tpl_slot(rel, tbase % P, P) == (int)(((long long)tbase + rel) % P) ? 0 : 1;
+                ++n_checked;
+            }
+    // the template store: two passes that differ in one lane id only do not share a template; equal
+    // ones do; a pass that is a prefix of another does not
+    {
+        std::vector<int> tl;
+        hk::OwnTplStore store(tl);
+        int a[8], b[8], la[8] = {1, 2, 3, 4, 5, 6, 7, 8}, lb[8] = {1, 2, 3, 4, 5, 6, 7, 8};
+        hk::own_pack(0, 0, hk::kOwnInit, 8, la, a);
+        hk::own_pack(5, 0, hk::kOwnInit | hk::kOwnFin, 8, la, a + 4);
+        lb[7] = 9;  // the lane kept in y
+        hk::own_pack(0, 0, hk::kOwnInit, 8, la, b);
+        hk::own_pack(5, 0, hk::kOwnInit | hk::kOwnFin, 8, lb, b + 4);
+        const int oa = store.add(a, 2), ob = store.add(b, 2), oa2 = store.add(a, 2), o1 = store.add(a, 1);
+        lb[7] = 8, lb[3] = 0;  // a lane kept in z | w
+        hk::own_pack(5, 0, hk::kOwnInit | hk::kOwnFin, 8, lb, b + 4);
+        const int oc = store.add(b, 2);
+        bad += (oa == 0 && ob == 2 && oa2 == oa && o1 == 4 && oc == 5 && store.distinct == 4 && tl.size() == 4 * 7) ? 0 : 1;
+        ++n_checked;
+    }
     std::printf("{\"ok\": %s, \"selftest\": %lld, \"bad\": %lld}\n", bad ? "false" : "true", n_checked, bad);
     return bad ? 1 : 0;
 }
@@ -168,56 +207,74 @@ int main(int argc, char** argv) {
             const double m = std::ldexp(1.0, (int)mag(rng));
             f[8 * e + k] = (rng() & 1 ? -1.0 : 1.0) * m * (1.0 + (double)(rng() >> 11) * 0x1p-53);
         }
-    std::vector<double> own_q(nN, 0.0), rows(std::max<long long>(pl.rows, 1), 0.0);
-    std::vector<char> q_set(nN, 0);
-    std::vector<double> slots(4096, 0.0);
-    std::vector<double> stage(8 * (size_t)epb * S);
     auto lane_of = [](const int* w, int j) { return hk::own_lane(w[1], w[2], w[3], j); };
-    long long bad = 0;
-    for (long long lb = 0; lb < Gp; ++lb) {
-        for (long long p0 = sc.bstart[lb]; p0 < sc.bstart[lb + 1]; p0 += S) {
-            const long long p1 = std::min<long long>(p0 + S, sc.bstart[lb + 1]);
-            std::fill(stage.begin(), stage.end(), 0.0);
-            for (long long p = p0; p < p1; ++p)
-                for (int l = 0; l < 8 * epb; ++l) {
-                    const long long e = (long long)sc.seq[p] * epb + l / 8;
-                    stage[(p - p0) * 8 * epb + l] = e < nE ? f[8 * e + l % 8] : 0.0;
-                }
-            for (int q = pl.off[p0]; q < pl.off[p0 + 1]; ++q) {
-                const int* w = &pl.list[4 * (size_t)q];
-                const int slot = hk::own_slot(w[1]), flags = hk::own_flags(w[1]), n = hk::own_n(w[1]);
-                if (flags & hk::kOwnExp) {
-                    for (int j = 0; j < n; ++j) rows[w[0] + (long long)j * slot] = stage[lane_of(w, j)];
-                    continue;
-                }
-                if (flags & hk::kOwnNop) continue;
-                double v = (flags & hk::kOwnInit) ? 0.0 : slots[slot];
-                for (int j = 0; j < n; ++j) v += stage[lane_of(w, j)];
-                if (flags & hk::kOwnFin) {
-                    if (q_set[w[0]]) ++bad;  // a node's sum is finished once
-                    q_set[w[0]] = 1;
-                    own_q[w[0]] = v;
-                } else {
-                    slots[slot] = v;
+    long long bad = 0, mismatch = 0;
+    // tpl: the template form, executed as the kernel does -- the super-batch's header, then its stored
+    // entries with the bases added and the slot derived (hakai_own_entry.hpp own_tpl_slot)
+    auto replay = [&](bool tpl) {
+        std::vector<double> own_q(nN, 0.0), rows(std::max<long long>(pl.rows, 1), 0.0);
+        std::vector<char> q_set(nN, 0);
+        std::vector<double> slots(4096, 0.0);
+        std::vector<double> stage(8 * (size_t)epb * S);
+        for (long long lb = 0; lb < Gp; ++lb) {
+            for (long long p0 = sc.bstart[lb]; p0 < sc.bstart[lb + 1]; p0 += S) {
+                const long long p1 = std::min<long long>(p0 + S, sc.bstart[lb + 1]);
+                std::fill(stage.begin(), stage.end(), 0.0);
+                for (long long p = p0; p < p1; ++p)
+                    for (int l = 0; l < 8 * epb; ++l) {
+                        const long long e = (long long)sc.seq[p] * epb + l / 8;
+                        stage[(p - p0) * 8 * epb + l] = e < nE ? f[8 * e + l % 8] : 0.0;
+                    }
+                const int* h = tpl ? &pl.hdr[4 * (size_t)p0] : nullptr;
+                const int q0 = tpl ? h[0] : pl.off[p0], q1 = tpl ? h[0] + hk::own_hdr_count(h[1]) : pl.off[p0 + 1];
+                if (tpl && q1 > pl.stored) ++bad;
+                for (int q = q0; q < q1; ++q) {
+                    const int* w = tpl ? &pl.tlist[4 * (size_t)q] : &pl.list[4 * (size_t)q];
+                    const int flags = hk::own_flags(w[1]), n = hk::own_n(w[1]);
+                    const bool exp = (flags & hk::kOwnExp) != 0;
+                    const long long target = tpl ? (long long)w[0] + (exp ? h[3] : h[2]) : w[0];
+                    int slot = hk::own_slot(w[1]);
+                    if (tpl && !exp) {
+                        slot = hk::own_tpl_slot(w[0], hk::own_hdr_sofs(h[1]), pl.P);
+                        if (slot < 0 || slot >= pl.P || slot != (int)(target % pl.P)) ++bad;
+                    }
+                    if (exp) {
+                        for (int j = 0; j < n; ++j) rows[target + (long long)j * slot] = stage[lane_of(w, j)];
+                        continue;
+                    }
+                    if (flags & hk::kOwnNop) continue;
+                    double v = (flags & hk::kOwnInit) ? 0.0 : slots[slot];
+                    for (int j = 0; j < n; ++j) v += stage[lane_of(w, j)];
+                    if (flags & hk::kOwnFin) {
+                        if (q_set[target]) ++bad;  // a node's sum is finished once
+                        q_set[target] = 1;
+                        own_q[target] = v;
+                    } else {
+                        slots[slot] = v;
+                    }
                 }
             }
         }
-    }
-    long long mismatch = 0;
-    for (int n = 0; n < nN; ++n) {
-        double ref = 0.0;
-        for (int j = ptr[n]; j < ptr[n + 1]; ++j) ref += f[inc0[j]];
-        double q = own_q[n];
-        for (int r = pl.rp[n]; r < pl.rp[n + 1]; ++r) q += rows[pl.ridx[r]];
-        if (std::memcmp(&q, &ref, sizeof q) != 0) ++mismatch;
-    }
+        for (int n = 0; n < nN; ++n) {
+            double ref = 0.0;
+            for (int j = ptr[n]; j < ptr[n + 1]; ++j) ref += f[inc0[j]];
+            double q = own_q[n];
+            for (int r = pl.rp[n]; r < pl.rp[n + 1]; ++r) q += rows[pl.ridx[r]];
+            if (std::memcmp(&q, &ref, sizeof q) != 0) ++mismatch;
+        }
+    };
+    replay(false);
+    if (pl.tpl) replay(true);
     const bool ok = mismatch == 0 && bad == 0;
     Fnv dg;
     dg.add(epb), dg.add(S), dg.add(sc.seq), dg.add(sc.bstart), dg.add(pl.off), dg.add(pl.list), dg.add(pl.rp), dg.add(pl.ridx);
     std::printf("{\"ok\": %s, \"planned\": true, \"elements\": %lld, \"nodes\": %d, \"epb\": %d, \"grid\": %lld, "
                 "\"superbatch\": %d, \"banded\": %d, \"rows\": %lld, \"entries\": %lld, \"slots\": %d, "
-                "\"slot_cap\": %d, \"round2\": %lld, \"mismatch\": %lld, \"double_fin\": %lld, \"digest\": \"%016llx\"}\n",
+                "\"slot_cap\": %d, \"round2\": %lld, \"mismatch\": %lld, \"double_fin\": %lld, \"digest\": \"%016llx\", "
+                "\"template_form\": %d, \"templates\": %lld, \"entries_stored\": %lld, \"passes\": %lld, "
+                "\"template_slots\": %d}\n",
                 ok ? "true" : "false", nE, nN, epb, Gp, S, sc.banded ? 1 : 0, pl.rows, pl.ne, pl.max_slots,
-                in.slot_cap[S - 1], pl.round2, mismatch, bad, dg.h);
+                in.slot_cap[S - 1], pl.round2, mismatch, bad, dg.h, pl.tpl ? 1 : 0, pl.templates,
+                pl.tpl ? pl.stored : pl.ne, pl.passes, pl.P);
     return ok ? 0 : 1;
 }
