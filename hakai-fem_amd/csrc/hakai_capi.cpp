@@ -29,6 +29,7 @@
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
 #include "hakai_loads.hpp"
+#include "hakai_mass_scale.hpp"
 #include "hakai_stable_dt.hpp"
 
 using hk::DevMat;
@@ -424,6 +425,7 @@ int hakai_destroy(hakai_ctx* c) {
     dfree(c->d_tstep);
     hkc::history_destroy(c);
     hkc::stable_dt_destroy(c);
+    hkc::mass_scale_destroy(c);
     hkc::comm_destroy(c);
     hkc::free_model(c);
     hkc::free_bc(c);
@@ -460,6 +462,7 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     (void)hipStreamSynchronize(c->stream);
     hkc::history_destroy(c);  // its buffers are sized for the previous mesh: enable again
     hkc::stable_dt_destroy(c);  // so is the stable-step scratch: the next call allocates it
+    hkc::mass_scale_destroy(c);  // a new model starts unscaled (d_mass is uploaded again below)
     hkc::free_model(c);
     // BC tables are sized for the previous mesh (the fused-BC per-dof table has 3nN entries): a new
     // model starts without BCs until hakai_set_bc runs again

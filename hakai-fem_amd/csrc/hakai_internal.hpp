@@ -18,6 +18,7 @@ struct Contact;  // contact search state (hakai_contact_state.hpp)
 struct History;  // history output state (hakai_history.hip)
 struct StableDt; // stable-time-step scratch (hakai_stable_dt.hip)
 struct Loads;    // external loads and rigid walls (hakai_loads.hip)
+struct MassScale; // selective mass scaling (hakai_mass_scale.hip)
 int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 }  // namespace hkc
@@ -139,6 +140,9 @@ struct hakai_ctx {
     // first call, and the Poisson ratios its material table needs next to h_young
     hkc::StableDt* sdt = nullptr;
     std::vector<double> h_poisson;     // per material
+    // selective mass scaling (hakai_mass_scale; hakai_mass_scale.hpp): the elements' added mass and the
+    // uploaded nodal mass, null until the first call (d_mass then holds the scaled mass)
+    hkc::MassScale* msc = nullptr;
     // external loads and rigid walls (hakai_set_loads, hakai_set_walls; hakai_loads.hpp): null without
     // both. d_ftot [3nN] is the step's total external force, contact plus loads plus walls (owned by
     // that state)

@@ -19,6 +19,10 @@
 // constant of the model, so a context's first call forms and stores it (k_stable_dt<false>) and the
 // later calls read it (k_stable_dt<true>, a fifth less arithmetic), the same bits.
 // Materials come from a per-call table in global memory: any number of them.
+// The gather, the exchanges and the sums are hakai_stable_dt_dev.hpp's elem_sums, which k_mass_need
+// (hakai_mass_scale.hip) shares. On a context with selective mass scaling in force
+// (hakai_mass_scale) k_stable_dt<true, true> runs: stable_finish_added with the element's added mass
+// instead of stable_finish; without it the two instantiations above, unchanged.
 // Per block: the minimum of each quantity with the lowest element id among equal values, and the
 // counts, combined over the wave with shuffles and ballots and over the four waves through 4 LDS
 // slots; one partial per block. k_stable_dt_finish, one block in a second launch, combines the
@@ -34,7 +38,10 @@
 #include "../../include/hakai_hip.h"
 #include "hakai_device.hpp"
 #include "hakai_internal.hpp"
+#include "hakai_mass_scale.hpp"
+#include "hakai_mass_scale_elem.hpp"
 #include "hakai_stable_dt.hpp"
+#include "hakai_stable_dt_dev.hpp"
 #include "hakai_stable_dt_elem.hpp"
 
 using hkc::dalloc;
@@ -44,9 +51,10 @@ using hkc::hip_fail;
 
 namespace {
 
-constexpr int kEPB = 32;        // elements per block
-constexpr int kThreads = 256;   // 8 lanes per element
-constexpr int kNone = INT_MAX;  // element id of "no active element": loses every tie
+using hk::sdt::kEPB;
+using hk::sdt::kNone;
+using hk::sdt::kThreads;
+using hk::sdt::take_min;
 
 // A partial result (a wave's, a block's); element ids local and 0-based.
 struct Part {
@@ -75,81 +83,27 @@ struct Args {
     double* safe_elem;   // [nE] or null
     Part* part;          // [ceil(nE / 32)]
     double* v0;          // [nE] the elements' V0: written by the first call, read by the later ones
+    const double* added; // [nE] selective mass scaling's added mass (k_stable_dt<true, true> only)
 };
-
-template <class I>
-__device__ __forceinline__ void take_min(double& v, I& id, double ov, I oid) {
-    if (ov < v || (ov == v && oid < id)) {
-        v = ov;
-        id = oid;
-    }
-}
-
-// The 24 sums S[c][i] = sum_k H_k[c][i] (t[1 + 8c + i] on lane k), left scattered: lane i gets the
-// three of node i. Partners k^1, k^2, k^4 in that order, each lane keeping the nodes whose bit
-// matches its own, so every sum is the pairwise tree ((0+1)+(2+3))+((4+5)+(6+7)) of allreduce8 and
-// of the header's stable_sum8 (an addition commutes), with 21 exchanges instead of 72.
-__device__ __forceinline__ void sum_scatter8(const double (&t)[hk::kStableTerms], double (&out)[3], int k) {
-    const bool b0 = (k & 1) != 0, b1 = (k & 2) != 0, b2 = (k & 4) != 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double w[4], u[2];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {  // nodes 2s + b0
-            const double lo = t[1 + 8 * c + 2 * s], hi = t[1 + 8 * c + 2 * s + 1];
-            w[s] = (b0 ? hi : lo) + hk::dpp<hk::kDppXor1>(b0 ? lo : hi);
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)    // nodes 4s + 2 b1 + b0
-            u[s] = (b1 ? w[2 * s + 1] : w[2 * s]) + hk::dpp<hk::kDppXor2>(b1 ? w[2 * s] : w[2 * s + 1]);
-        out[c] = (b2 ? u[1] : u[0]) + __shfl_xor(b2 ? u[0] : u[1], 4, 8);
-    }
-}
 
 // kHaveV0 false: a context's first call, which also forms every element's V0 (a constant of the
 // model) and stores it; true: the later calls, which read it -- the same bits either way.
-template <bool kHaveV0>
+// kAdded: selective mass scaling is in force (it has formed V0), the element's mass is m0 + added.
+template <bool kHaveV0, bool kAdded>
 __global__ __launch_bounds__(kThreads) void k_stable_dt(Args a) {
     const int tid = threadIdx.x, k = tid & 7;
     const long long e = (long long)blockIdx.x * kEPB + (tid >> 3);
     const bool in = e < a.nE;
     const long long ee = in ? e : a.nE - 1;  // lanes past the end compute the last element and drop it
     const bool active = in && a.flag[ee] == 1;
-    const long long n = a.conn[8 * ee + k];
-    double Xk[3], xk[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        Xk[c] = a.coord[3 * n + c];
-        xk[c] = a.coord[3 * n + c] + a.u[3 * n + c];
-    }
-    double V0;
-    if constexpr (kHaveV0) {
-        V0 = a.v0[ee];
-    } else {
-        double X[8][3], d0[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) X[i][c] = __shfl(Xk[c], i, 8);
-        const double det0 = hk::stable_det0(k, X);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) d0[i] = __shfl(det0, i, 8);
-        V0 = hk::stable_v0(d0);
-        if (in && k == 0) a.v0[e] = V0;
-    }
-    double x[8][3];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) x[i][c] = __shfl(xk[c], i, 8);
-    double t[hk::kStableTerms];
-    hk::stable_gp(k, x, t);
-    const double V = hk::allreduce8(t[0]), ss = hk::allreduce8(t[25]);
-    double Sn[3];
-    sum_scatter8(t, Sn, k);
-    const double gg = hk::allreduce8(hk::stable_node_gg(Sn[0], Sn[1], Sn[2], V));
+    hk::sdt::ElemSums s;
+    hk::sdt::elem_sums<kHaveV0>(a.coord, a.u, a.conn, a.v0, ee, k, in, s);
     double est, safe;
-    hk::stable_finish(V, gg, ss, V0, hk::stable_amax(x), a.mats[a.mat[ee]], &est, &safe);
+    if constexpr (kAdded)
+        hk::stable_finish_added(s.V, s.gg, s.ss, s.V0, hk::stable_amax(s.x), a.mats[a.mat[ee]], a.added[ee], &est,
+                                &safe);
+    else
+        hk::stable_finish(s.V, s.gg, s.ss, s.V0, hk::stable_amax(s.x), a.mats[a.mat[ee]], &est, &safe);
     if (!active) {
         est = HUGE_VAL;
         safe = HUGE_VAL;
@@ -263,6 +217,37 @@ void stable_dt_destroy(hakai_ctx* c) {
     c->sdt = nullptr;
 }
 
+// The scratch at the first call, and this call's material table on its way to the device (ordered on
+// the context's stream; h_mats holds it until the caller synchronises).
+int stable_dt_prepare(hakai_ctx* c, double mass_scaling) {
+    const long long nE = c->nE, nb = (nE + kEPB - 1) / kEPB;
+    if (!c->sdt) {
+        StableDt* s = new StableDt();
+        c->sdt = s;
+        if (dalloc(&s->d_part, (size_t)nb) != hipSuccess || dalloc(&s->d_res, 1) != hipSuccess ||
+            dalloc(&s->d_mats, (size_t)c->nmat) != hipSuccess || dalloc(&s->d_v0, (size_t)nE) != hipSuccess) {
+            stable_dt_destroy(c);
+            return fail(HAKAI_ERR_DEVICE, "stable_dt: hipMalloc of the scratch failed");
+        }
+    }
+    StableDt* s = c->sdt;
+    s->h_mats.resize((size_t)c->nmat);
+    for (int i = 0; i < c->nmat; ++i)
+        s->h_mats[i] = hk::stable_mat(c->h_young[i], c->h_poisson[i], c->h_mats[i].density, mass_scaling);
+    HIPCHK(hipMemcpyAsync(s->d_mats, s->h_mats.data(), (size_t)c->nmat * sizeof(hk::StableMat), hipMemcpyHostToDevice,
+                          c->stream));
+    return 0;
+}
+
+const hk::StableMat* stable_dt_mats(const hakai_ctx* c) { return c->sdt ? c->sdt->d_mats : nullptr; }
+double* stable_dt_v0(const hakai_ctx* c, bool* have) {
+    *have = c->sdt && c->sdt->have_v0;
+    return c->sdt ? c->sdt->d_v0 : nullptr;
+}
+void stable_dt_v0_formed(hakai_ctx* c) {
+    if (c->sdt) c->sdt->have_v0 = true;
+}
+
 }  // namespace hkc
 
 extern "C" int hakai_stable_dt(hakai_ctx* c, double mass_scaling, double d_time, hakai_stable_dt_t* out,
@@ -278,24 +263,11 @@ extern "C" int hakai_stable_dt(hakai_ctx* c, double mass_scaling, double d_time,
     r.element_est = r.element_safe = 0;
     r.n_active = r.n_est_below = r.n_safe_below = 0;
     if (nE > 0) {
-        if (!c->sdt) {
-            hkc::StableDt* s = new hkc::StableDt();
-            c->sdt = s;
-            if (dalloc(&s->d_part, (size_t)nb) != hipSuccess || dalloc(&s->d_res, 1) != hipSuccess ||
-                dalloc(&s->d_mats, (size_t)c->nmat) != hipSuccess || dalloc(&s->d_v0, (size_t)nE) != hipSuccess) {
-                hkc::stable_dt_destroy(c);
-                return fail(HAKAI_ERR_DEVICE, "stable_dt: hipMalloc of the scratch failed");
-            }
-        }
+        if (int rc = hkc::stable_dt_prepare(c, mass_scaling)) return rc;
         hkc::StableDt* s = c->sdt;
         if (dt_est_elem && !s->d_est) HIPCHK(dalloc(&s->d_est, (size_t)nE));
         if (dt_safe_elem && !s->d_safe) HIPCHK(dalloc(&s->d_safe, (size_t)nE));
-        s->h_mats.resize((size_t)c->nmat);
-        for (int i = 0; i < c->nmat; ++i)
-            s->h_mats[i] = hk::stable_mat(c->h_young[i], c->h_poisson[i], c->h_mats[i].density, mass_scaling);
         hipStream_t st = c->stream;
-        HIPCHK(hipMemcpyAsync(s->d_mats, s->h_mats.data(), (size_t)c->nmat * sizeof(hk::StableMat),
-                              hipMemcpyHostToDevice, st));
         Args a;
         a.coord = c->d_coord;
         a.u = c->d_u[c->sv.cur];
@@ -309,10 +281,15 @@ extern "C" int hakai_stable_dt(hakai_ctx* c, double mass_scaling, double d_time,
         a.safe_elem = dt_safe_elem ? s->d_safe : nullptr;
         a.part = s->d_part;
         a.v0 = s->d_v0;
-        if (s->have_v0)
-            hipLaunchKernelGGL(k_stable_dt<true>, dim3((unsigned)nb), dim3(kThreads), 0, st, a);
+        a.added = hkc::mass_scale_added(c);
+        if (a.added && s->have_v0)
+            hipLaunchKernelGGL((k_stable_dt<true, true>), dim3((unsigned)nb), dim3(kThreads), 0, st, a);
+        else if (a.added)
+            return fail(HAKAI_ERR_STATE, "stable_dt: mass scaling in force without the elements' V0");
+        else if (s->have_v0)
+            hipLaunchKernelGGL((k_stable_dt<true, false>), dim3((unsigned)nb), dim3(kThreads), 0, st, a);
         else
-            hipLaunchKernelGGL(k_stable_dt<false>, dim3((unsigned)nb), dim3(kThreads), 0, st, a);
+            hipLaunchKernelGGL((k_stable_dt<false, false>), dim3((unsigned)nb), dim3(kThreads), 0, st, a);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_stable_dt_finish, dim3(1), dim3(kThreads), 0, st, (const Part*)s->d_part, nb, s->d_res);
         HIPCHK(hipGetLastError());

@@ -62,6 +62,13 @@ class StableDtT(ctypes.Structure):
                 ("n_active", c_int64), ("n_est_below", c_int64), ("n_safe_below", c_int64)]
 
 
+class MassScaleT(ctypes.Structure):
+    """hakai_mass_scale_t: the counts, the largest mass factor, the mass added, the minimum dt_safe after."""
+    _fields_ = [("n_active", c_int64), ("n_scaled", c_int64), ("n_changed", c_int64), ("n_capped", c_int64),
+                ("n_unfixable", c_int64), ("max_factor_reached", c_double), ("element_factor", c_int64),
+                ("mass_added", c_double), ("dt_safe", c_double), ("element_safe", c_int64)]
+
+
 class LoadsT(ctypes.Structure):
     """hakai_loads_t: amplitude tables, concentrated loads, gravity, face pressure."""
     _fields_ = [("n_amp", c_int32), ("amp_n", PI32), ("amp_off", PI64), ("amp_time", PD), ("amp_value", PD),
@@ -88,7 +95,9 @@ class InpModelT(ctypes.Structure):
                 ("n_ic_dofs", c_int64), ("ic_dofs", PI64), ("ic_values", PD), ("n_instance", c_int32),
                 ("instance_node_offset", PI64), ("instance_element_offset", PI64),
                 ("instance_nElement", PI64), ("n_cp", c_int32), ("cp_instance", PI32), ("cp_elem_off", PI64),
-                ("cp_elems", PI64), ("loads", LoadsT), ("walls", WallsT)]
+                ("cp_elems", PI64), ("loads", LoadsT), ("walls", WallsT),
+                ("vms_set", c_int32), ("vms_repeat", c_int32), ("vms_dt", c_double), ("vms_safety", c_double),
+                ("vms_max_factor", c_double)]
 
 
 class HakaiError(RuntimeError):
@@ -165,6 +174,9 @@ def lib() -> ctypes.CDLL:
         "hakai_stable_dt": (c_int, [c_void_p, c_double, c_double, POINTER(StableDtT), PD, PD]),
         "hakai_stable_dt_combine": (c_int, [c_int32, POINTER(StableDtT), POINTER(StableDtT)]),
         "hakai_stable_dt_write_csv": (c_int, [c_char_p, c_int64, PI64, POINTER(StableDtT), c_double]),
+        "hakai_mass_scale": (c_int, [c_void_p, c_double, c_double, c_double, c_double, POINTER(MassScaleT)]),
+        "hakai_mass_scale_get": (c_int, [c_void_p, PD, PD]),
+        "hakai_clear_mass_scale": (c_int, [c_void_p]),
         "hakai_set_loads": (c_int, [c_void_p, POINTER(LoadsT)]),
         "hakai_clear_loads": (c_int, [c_void_p]),
         "hakai_load_force": (c_int, [c_void_p, c_double, c_double, PD]),
@@ -201,6 +213,7 @@ def exported_symbols() -> list[str]:
         "hakai_history_enable", "hakai_history_disable", "hakai_history_count", "hakai_history_read",
         "hakai_history_write_csv", "hakai_history_combine", "hakai_inp_history_sets",
         "hakai_stable_dt", "hakai_stable_dt_combine", "hakai_stable_dt_write_csv",
+        "hakai_mass_scale", "hakai_mass_scale_get", "hakai_clear_mass_scale",
         "hakai_set_loads", "hakai_clear_loads", "hakai_load_force",
         "hakai_set_walls", "hakai_clear_walls", "hakai_wall_force",
     ]

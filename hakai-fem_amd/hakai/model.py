@@ -192,6 +192,10 @@ class Model:
     loads: Loads | None = None
     # rigid walls (*Rigid Wall of a deck; Solver applies them); None = no wall
     walls: Walls | None = None
+    # *Variable Mass Scaling of a deck: dict(dt=target or None for the stepped dt, safety=, max_factor=,
+    # repeat=True for repeat=output); None = the deck has none. The one-GPU drivers (hakai.hakai, the
+    # hakai CLI) apply it; a Solver does not on its own -- call Solver.mass_scale(**...) where wanted
+    variable_mass_scaling: dict | None = None
 
     def c_contact_pairs(self):
         """(n_cp, cp_instance int32[2n], cp_elem_off int64[2n+1], cp_elems int64[]) for the C ABI."""
@@ -388,8 +392,13 @@ def read_inp(path: str) -> Model:
                           _arr(wl.damping, nw, np.float64), _arr(wl.friction, nw, np.float64),
                           [wnodes[noff[w]:noff[w + 1]].copy() for w in range(nw)],
                           [(wt[wo[a]:wo[a] + wn[a]].copy(), wv[wo[a]:wo[a] + wn[a]].copy()) for a in range(wl.n_amp)])
+        vms = None
+        if m.vms_set:
+            vms = dict(dt=float(m.vms_dt) if m.vms_dt > 0 else None, safety=float(m.vms_safety),
+                       max_factor=float(m.vms_max_factor), repeat=bool(m.vms_repeat))
         return Model(coord, elem, emat, mats, bc, ic_d, ic_v, m.d_time, m.end_time, m.mass_scaling,
                      m.contact_flag, einst, name=str(path), contact_pairs=cps,
-                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]), loads=loads, walls=walls)
+                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]), loads=loads, walls=walls,
+                     variable_mass_scaling=vms)
     finally:
         L.hakai_inp_free(out)

@@ -236,6 +236,10 @@ def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device:
     if glob.walls is not None and not glob.walls.empty:
         raise ValueError(f"{fname}: the deck has rigid walls (*Rigid Wall); the N-GPU driver does not apply walls "
                          "yet -- run it on one GPU (hakai.hakai / the hakai CLI)")
+    if glob.variable_mass_scaling is not None:
+        raise ValueError(f"{fname}: the deck has *Variable Mass Scaling; the N-GPU driver does not scale mass yet "
+                         "(a shared node needs the neighbour rank's elements) -- run it on one GPU (hakai.hakai / "
+                         "the hakai CLI)")
     gdiag, _ = glob.lumped_mass()
     dt = glob.dt
     time_num = glob.end_time / dt

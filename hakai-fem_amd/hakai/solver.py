@@ -15,7 +15,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._abi import StableDtT, StateT, check, lib, ptr
+from ._abi import MassScaleT, StableDtT, StateT, check, lib, ptr
 from .model import Loads, Model, Walls
 
 I64 = ctypes.c_int64
@@ -306,6 +306,33 @@ class Solver:
             out.update(dt_est_elem=est, dt_safe_elem=safe)
         return out
 
+    # -- selective mass scaling ----------------------------------------------------------------------
+    def mass_scale(self, dt_target: float | None = None, safety: float = 0.9, max_factor: float = float("inf"),
+                   mass_scaling: float | None = None) -> dict:
+        """Add mass to the elements whose guaranteed stable step ``dt_safe`` is below ``dt_target`` at
+        the current state, as much as brings it there (hakai_mass_scale); no other element changes.
+        Defaults: the model's stepped ``dt`` and its ``mass_scaling``. Returns the fields of
+        hakai_mass_scale_t: ``n_active``, ``n_scaled``, ``n_changed``, ``n_capped``, ``n_unfixable``,
+        ``max_factor_reached`` with ``element_factor``, ``mass_added``, and the minimum ``dt_safe``
+        after the call with ``element_safe``. Mass only grows; the same call again changes nothing."""
+        m = self.model
+        r = MassScaleT()
+        check(self.L.hakai_mass_scale(self.ctx, float(m.mass_scaling if mass_scaling is None else mass_scaling),
+                                      float(m.dt if dt_target is None else dt_target), float(safety),
+                                      float(max_factor), ctypes.byref(r)))
+        return {name: getattr(r, name) for name, _ in MassScaleT._fields_}
+
+    def mass_scale_state(self) -> dict:
+        """``elem_added`` (nElement: the mass added to each of the element's 8 nodes) and ``diag_M``
+        (3 nNode: the mass the steps read) of the context (hakai_mass_scale_get)."""
+        added, diag = np.zeros(self.model.nElement), np.zeros(3 * self.model.nNode)
+        check(self.L.hakai_mass_scale_get(self.ctx, ptr(added), ptr(diag)))
+        return dict(elem_added=added, diag_M=diag)
+
+    def clear_mass_scale(self):
+        """Back to the uploaded mass, bit for bit (hakai_clear_mass_scale)."""
+        check(self.L.hakai_clear_mass_scale(self.ctx))
+
     # -- multi-GPU ---------------------------------------------------------------------------------
     def comm_init(self, rank: int, nranks: int, uid: bytes):
         buf = (ctypes.c_uint8 * 128).from_buffer_copy(uid)
@@ -499,8 +526,25 @@ def read_history_csv(path: str) -> dict:
     return dict(sets=sets, steps=steps, time=time, values=values)
 
 
+MASS_SCALE_CSV = ("step", "dt_target", "n_active", "n_scaled", "n_changed", "n_capped", "n_unfixable", "mass_added",
+                  "max_factor_reached", "element_factor", "dt_safe", "element_safe")
+
+
+def read_mass_scale_csv(path: str) -> list[dict]:
+    """A driver's mass_scale.csv back as one dict per application: the same doubles (step and dt_target,
+    then Solver.mass_scale()'s fields)."""
+    with open(path) as fh:
+        head = fh.readline().strip().split(",")
+        assert tuple(head) == MASS_SCALE_CSV, head
+        flt = ("dt_target", "mass_added", "max_factor_reached", "dt_safe")
+        return [{k: (float(v) if k in flt else int(v)) for k, v in zip(head, ln.strip().split(","))}
+                for ln in fh if ln.strip()]
+
+
 def hakai(fname: str, out_dir: str = "temp", device: int = 0, verbose: bool = True):
     """HAKAI(fname) (v2/HAKAI_j.jl:81): run the deck on the GPU and write out_dir/file%03d.vtk.
     Env HAKAI_HISTORY=<stride> also writes out_dir/history.csv, env HAKAI_DT_CHECK=1 also
-    out_dir/stable_dt.csv (hakai_run_inp)."""
+    out_dir/stable_dt.csv; a deck with *Variable Mass Scaling (Model.variable_mass_scaling) gets its
+    mass scaled after the reset (repeat=output: at every output state too) and out_dir/mass_scale.csv
+    (hakai_run_inp)."""
     check(lib().hakai_run_inp(str(fname).encode(), str(out_dir).encode(), device, int(verbose)))

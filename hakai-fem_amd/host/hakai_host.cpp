@@ -957,6 +957,41 @@ void parse(const char* path, Owned& o) {
     p.walls.friction = o.wl_fric.data();
     p.walls.node_off = o.wl_node_off.data();
     p.walls.nodes = o.wl_nodes.data();
+
+    // ---- selective mass scaling: *Variable Mass Scaling [, dt=..] [, safety=..] [, max factor=..]
+    // [, repeat=output]. A HAKAI keyword (the reference's reader skips it); an unknown parameter, a
+    // malformed or out-of-range value or a second keyword line is an error, never a silent skip.
+    p.vms_set = 0;
+    p.vms_repeat = 0;
+    p.vms_dt = 0.0;
+    p.vms_safety = 0.9;
+    p.vms_max_factor = HUGE_VAL;
+    for (long long li = 1; li <= n; ++li) {
+        if (!has(line(li), "*Variable Mass Scaling")) continue;
+        if (p.vms_set) throw ParseError{"*Variable Mass Scaling: more than one"};
+        p.vms_set = 1;
+        const auto head = split(nospace(line(li)), ',', false);
+        if (head.empty() || head[0] != "*VariableMassScaling")
+            throw ParseError{"*Variable Mass Scaling: malformed keyword line"};
+        for (size_t k = 1; k < head.size(); ++k) {
+            const std::string& tok = head[k];
+            if (tok.rfind("dt=", 0) == 0) {
+                p.vms_dt = parse_f(after(tok, "dt="));
+                if (!(p.vms_dt > 0.0) || std::isinf(p.vms_dt)) throw ParseError{"*Variable Mass Scaling: dt must be positive"};
+            } else if (tok.rfind("safety=", 0) == 0) {
+                p.vms_safety = parse_f(after(tok, "safety="));
+                if (!(p.vms_safety > 0.0 && p.vms_safety <= 1.0))
+                    throw ParseError{"*Variable Mass Scaling: safety must be in (0, 1]"};
+            } else if (tok.rfind("maxfactor=", 0) == 0) {
+                p.vms_max_factor = parse_f(after(tok, "maxfactor="));
+                if (!(p.vms_max_factor >= 1.0)) throw ParseError{"*Variable Mass Scaling: max factor must be >= 1"};
+            } else if (tok == "repeat=output") {
+                p.vms_repeat = 1;
+            } else {
+                throw ParseError{"*Variable Mass Scaling: unknown parameter " + tok};
+            }
+        }
+    }
 }
 
 void pusai_table(double P[8][3][8]) {  // cal_Pusai_hexa, v2/HAKAI_j.jl:1895-1943
@@ -1154,6 +1189,40 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
         }
         return 0;
     };
+    // *Variable Mass Scaling: hakai_mass_scale at state 0 and, with repeat=output, at every output
+    // state before the next chunk of steps; one line per application in out_dir/mass_scale.csv
+    const double ms_target = M->vms_dt > 0.0 ? M->vms_dt : d_time;
+    std::FILE* ms_csv = nullptr;
+    struct CloseF {
+        std::FILE*& f;
+        ~CloseF() { if (f) std::fclose(f); }
+    } close_ms{ms_csv};
+    auto scale_mass = [&](long long step) -> int {
+        hakai_mass_scale_t s;
+        int q = hakai_mass_scale(c, M->mass_scaling, ms_target, M->vms_safety, M->vms_max_factor, &s);
+        if (q) return q;
+        if (std::fprintf(ms_csv, "%lld,%.17g,%lld,%lld,%lld,%lld,%lld,%.17g,%.17g,%lld,%.17g,%lld\n", step, ms_target,
+                         (long long)s.n_active, (long long)s.n_scaled, (long long)s.n_changed, (long long)s.n_capped,
+                         (long long)s.n_unfixable, s.mass_added, s.max_factor_reached, (long long)s.element_factor,
+                         s.dt_safe, (long long)s.element_safe) < 0)
+            return fail(HAKAI_ERR_IO, "mass_scale.csv: write failed");
+        if (verbose && s.n_changed > 0)
+            std::fprintf(stderr, "mass_scale: step %lld: %lld of %lld elements changed (%lld scaled, %lld capped, %lld "
+                         "unfixable), mass added %.6e, largest factor %.6g (element %lld), dt_safe %.6e\n", step,
+                         (long long)s.n_changed, (long long)s.n_active, (long long)s.n_scaled, (long long)s.n_capped,
+                         (long long)s.n_unfixable, s.mass_added, s.max_factor_reached, (long long)s.element_factor,
+                         s.dt_safe);
+        return 0;
+    };
+    if (M->vms_set) {
+        const std::string path = std::string(out_dir) + "/mass_scale.csv";
+        (void)mkdir(out_dir, 0755);  // (the VTK writer makes it too, with its first file)
+        ms_csv = std::fopen(path.c_str(), "w");
+        if (!ms_csv) return fail(HAKAI_ERR_IO, "%s: cannot open", path.c_str());
+        std::fprintf(ms_csv, "step,dt_target,n_active,n_scaled,n_changed,n_capped,n_unfixable,mass_added,"
+                             "max_factor_reached,element_factor,dt_safe,element_safe\n");
+        if ((r = scale_mass(0))) return r;
+    }
     if (dt_check && (r = check_dt(0))) return r;
     if ((r = output(0))) return r;
     int i_out = 1;
@@ -1172,6 +1241,7 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
             std::fflush(stdout);
         }
         if (d_out > 0 && t1 % d_out == 0) {
+            if (M->vms_set && M->vms_repeat && t1 < n_steps && (r = scale_mass(t1))) return r;
             if (dt_check && (r = check_dt(t1))) return r;
             if ((r = output(i_out))) return r;
             ++i_out;

@@ -339,6 +339,59 @@ int hakai_stable_dt_combine(int32_t n_ranks, const hakai_stable_dt_t* parts, hak
 int hakai_stable_dt_write_csv(const char* path, int64_t n, const int64_t* steps, const hakai_stable_dt_t* rec,
                               double d_time);
 
+/* ---- selective mass scaling: add element mass up to a target stable step ---------------------- */
+/* The reference knows only *Fixed Mass Scaling, which multiplies every node's mass. hakai_mass_scale
+ * adds mass only to the elements whose own dt_safe (above) is below a target, as much as brings it
+ * there; the elementwise bound holds for any per-element masses, so dt_target is then provably stable
+ * for the elastic stiffness. There is no reference counterpart: the definition is this text and
+ * csrc/hakai_mass_scale_elem.hpp (one host/device header, compiled without contraction).
+ * State: added_e >= 0, the mass added to each of element e's 8 nodes; 0 until a call raises it; it
+ * survives the element's deletion (the reference never takes a deleted element's mass back).
+ * A call applies, to every active element at the current configuration, with V, gg = sum g~^2,
+ * ss = sum_k s_k, V0 and the material constants exactly as hakai_stable_dt forms them:
+ *     kappa = (Kb V) gg + two_mu ss;   m0 = rho8 V0;   half = (0.5 dt_target) / safety
+ *     a = kappa (half half) - m0;   cap = (max_factor - 1) m0;   a > cap: a = cap, "capped"
+ *     added_new = a > added_prev ? a : added_prev
+ * An element with V0 <= 0, V == 0 or a kappa that is not finite is "unfixable" and keeps its added
+ * mass; a deleted element is untouched. Mass only grows; the same call at the same state changes no
+ * bit and reports n_changed = 0. For safety <= 1 - 2^-40, every active element that is neither capped
+ * nor unfixable then has dt_safe = 2 sqrt((m0 + added_new) / kappa) >= dt_target.
+ * Nodal mass: M_n = M0_n + sum of added_e over the node's incidences in ascending (8e + i) order,
+ * every addition rounded once, zeros included (an element that lists a node twice adds twice); M0 is
+ * the uploaded mass, copied at the first call; M_n is always summed from it. Every kernel of a step
+ * reads that mass (the nodal update, gravity and walls, history, contact). Mid-run the added mass
+ * takes the node's velocity (momentum grows by dm v), and under gravity it has weight.
+ * The call needs a state, runs on the context's stream and synchronises; it is callable at state 0
+ * or between hakai_step calls. It writes the mass buffer in place: captured step graphs stay valid
+ * and run with the new mass. A call that changed some element restarts an enabled history like a
+ * state upload (KE and P change their meaning); so does a clear that removed mass.
+ * hakai_stable_dt on a scaled context evaluates m0 + added_e (dt_est stretched by
+ * sqrt((m0 + added_e) / m0)); unscaled elements keep their bits.
+ * HAKAI_ERR_ARG (nothing changes, the scaling stays in force): mass_scaling or dt_target not positive
+ * and finite, safety outside (0, 1], max_factor < 1 or NaN. HAKAI_ERR_STATE: no state; a context with
+ * a communicator (a shared node needs the neighbour rank's elements: refused, never dropped).
+ * hakai_upload_model clears the scaling; hakai_set_bc, hakai_reset_state and hakai_upload_state keep it. */
+typedef struct {
+    int64_t n_active;      /* active elements */
+    int64_t n_scaled;      /* elements with added > 0 after the call (deleted ones included: their mass stays) */
+    int64_t n_changed;     /* active elements whose added mass this call raised */
+    int64_t n_capped, n_unfixable;   /* of the active elements */
+    double max_factor_reached;       /* max (m0 + added) / m0 over the active elements with V0 > 0 (1 if none) */
+    int64_t element_factor;          /* its element, 1-based + the element offset; equal values: the lowest id; 0: none */
+    double mass_added;     /* sum_e 8 added_e in one fixed binary tree in element order: the same bits for every grid */
+    double dt_safe;        /* the minimum of dt_safe over the active elements AFTER the call (+inf: none) */
+    int64_t element_safe;
+} hakai_mass_scale_t;
+/* mass_scaling > 0 (the factor diag_M was built with), dt_target > 0, safety in (0, 1] (the drivers
+ * take 0.9: a choice, not a measurement), max_factor >= 1 (+inf: no cap). */
+int hakai_mass_scale(hakai_ctx* ctx, double mass_scaling, double dt_target, double safety, double max_factor,
+                     hakai_mass_scale_t* out);
+/* elem_added: nElement values (zeros without scaling) or NULL; diag_M: 3 nNode values, the mass the
+ * steps read, per dof, or NULL. */
+int hakai_mass_scale_get(hakai_ctx* ctx, double* elem_added, double* diag_M);
+/* Restores the uploaded mass bit for bit and frees the scaling's state. */
+int hakai_clear_mass_scale(hakai_ctx* ctx);
+
 /* ---- external loads: nodal forces, gravity and follower face pressure ------------------------- */
 /* The reference has no loads: nothing here has a counterpart in it. With loads set, every hakai_step
  * (captured graphs included) forms, in one launch after the contact search and before the nodal
@@ -605,6 +658,18 @@ typedef struct {
      * amplitude, a malformed or missing data line and a 33rd wall are parse errors. A deck without
      * the keyword has n_wall 0. */
     hakai_walls_t walls;
+    /* *Variable Mass Scaling [, dt=TARGET] [, safety=S] [, max factor=F] [, repeat=output]: a HAKAI
+     * keyword (the reference's reader skips it; the name does not contain "*Fixed Mass Scaling", whose
+     * parse is untouched). The one-GPU drivers call hakai_mass_scale after hakai_reset_state and, with
+     * repeat=output, again at every VTK output state before the next chunk of steps. Defaults: dt 0 (=
+     * the stepped d_time, increment * sqrt(mass_scaling)), safety 0.9, max factor +inf (no cap), state
+     * 0 only. An unknown parameter, a malformed value, dt <= 0, safety outside (0, 1], max factor < 1 or
+     * a second keyword line are parse errors. A deck without the keyword has vms_set 0. */
+    int32_t vms_set;        /* 1: the deck has the keyword */
+    int32_t vms_repeat;     /* 1: repeat=output */
+    double vms_dt;          /* the target; 0: the stepped d_time */
+    double vms_safety;
+    double vms_max_factor;
 } hakai_inp_model_t;
 
 int hakai_inp_read(const char* path, hakai_inp_model_t** out);
@@ -657,6 +722,11 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
  * out_dir/history.csv (hakai_history_write_csv) at the end: set "all", then "inst<i>" per instance,
  * then "bc<g>" per *Boundary group (the nodes of its dofs), 15 sets at most (verbose: the ones left
  * out are named on stderr); the ring holds the whole run. Without the variable nothing changes.
+ * A deck with *Variable Mass Scaling: hakai_mass_scale after the reset (and, with repeat=output, at
+ * every VTK output state but the last, before HAKAI_DT_CHECK's evaluation of that state and the next
+ * chunk of steps), one line per application in out_dir/mass_scale.csv: step,dt_target,n_active,n_scaled,
+ * n_changed,n_capped,n_unfixable,mass_added,max_factor_reached,element_factor,dt_safe,element_safe
+ * (doubles as %.17g); verbose: one stderr line per application that changed something.
  * Env HAKAI_DT_CHECK=1 records hakai_stable_dt at state 0 and at every VTK output (the deck's
  * mass_scaling, the stepped d_time = increment * sqrt(mass_scaling)) and writes
  * out_dir/stable_dt.csv (hakai_stable_dt_write_csv) at the end; verbose: one stderr line the first
