@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/hakai_hip.h"
+#include "hakai_conn_plan.hpp"
 #include "hakai_history.hpp"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
@@ -72,6 +73,8 @@ static void free_model(hakai_ctx* c) {
     dfree(c->d_u[1]);
     dfree(c->d_mass);
     dfree(c->d_conn);
+    c->d_conn_rec.free();
+    c->conn_P = 0;
     dfree(c->d_flag);
     dfree(c->d_mat);
     dfree(c->d_mats);
@@ -545,6 +548,18 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
         HIPCHK(hipMemcpyAsync(c->d_mat, mat.data(), nEp * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(c->d_inc_row, inc.data(), 8 * nE * sizeof(int), hipMemcpyHostToDevice, s));
     }
+    {  // connectivity templates: base node + shared offset pattern, where the mesh has few patterns
+        hk::ConnPlan cp;
+        if (nE && hk::conn_plan(conn.data(), nEp, cp)) {
+            std::vector<unsigned> rp(cp.rec);  // the records, then the table
+            rp.insert(rp.end(), cp.pat.begin(), cp.pat.end());
+            HIPCHK(c->d_conn_rec.upload(rp, s));
+            HIPCHK(hipStreamSynchronize(s));  // (rp goes out of scope)
+            c->conn_P = cp.P;
+            c->conn_bits = cp.base_bits;
+            c->conn_bytes = cp.bytes;
+        }
+    }
     HIPCHK(hipMemcpyAsync(c->d_mats, c->h_mats.data(), nMat * sizeof(DevMat), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_inc_ptr, ptr.data(), (nN + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     if (maxinc <= 8) HIPCHK(dalloc(&c->d_inc8, 8 * (size_t)nN));  // padded table for the unrolled gather
@@ -845,7 +860,7 @@ int hakai_stat(hakai_ctx* c, const char* key, int64_t* value) {
     if (!c || !key || !value) return fail(HAKAI_ERR_ARG, "null");
     if (!std::strcmp(key, "graph_steps")) *value = c->graph_steps;
     else if (!std::strcmp(key, "exchange_retries")) *value = c->exchange_retries;
-    else if (!std::strncmp(key, "own_", 4)) return hkc::own_stat(c, key, value);
+    else if (!std::strncmp(key, "own_", 4) || !std::strncmp(key, "conn_", 5)) return hkc::own_stat(c, key, value);
     else return fail(HAKAI_ERR_ARG, "unknown stat '%s'", key);
     return 0;
 }
@@ -921,6 +936,11 @@ int hakai_set_tuning(hakai_ctx* c, const char* key, int64_t value) {
         return c->d_inc8 ? 0 : fail(HAKAI_ERR_STATE, "padded incidence table unavailable (>8 incidences)");
     }
     if (!std::strncmp(key, "own_", 4)) return hkc::own_tuning(c, key, value);
+    if (!std::strcmp(key, "conn_templates")) {  // (every tuning call drops the captured graphs, above)
+        if (value != 0 && value != 1) return fail(HAKAI_ERR_ARG, "conn_templates must be 0 or 1");
+        c->conn_templates = (int)value;
+        return 0;
+    }
     if (!std::strcmp(key, "graph")) {
         if (value < 0 || value > 1024 || (value & 1)) return fail(HAKAI_ERR_ARG, "graph must be 0 or an even step count <= 1024");
         c->graph = (int)value;

@@ -45,6 +45,13 @@ struct hakai_ctx {
     hkc::StepView sv;            // the host's view of the stepping state (hakai_step_view.hpp)
     double* d_mass = nullptr;
     int* d_conn = nullptr;
+    // connectivity templates (hakai_conn_plan.hpp), planned by hakai_upload_model: the element
+    // kernel's packed records [nEp] followed by the offset table [conn_P][8]; conn_P 0: the mesh has no
+    // compressed form
+    hkc::DevBuf<unsigned> d_conn_rec;
+    int conn_P = 0, conn_bits = 0;
+    long long conn_bytes = 0;    // connectivity bytes per launch of the compressed form
+    int conn_templates = 1;      // tuning "conn_templates": use the compressed form where it exists
     int* d_flag = nullptr;
     int* d_mat = nullptr;
     hk::DevMat* d_mats = nullptr;

@@ -87,14 +87,31 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
 }
 
-template <bool EXACT = false>
+// CT: connectivity templates (ElemArgs::conn_rec) -- in.n is left to the caller, which loads the
+// element's record (conn_rec) and resolves the node in two more steps (conn_off, conn_node).
+template <bool EXACT = false, bool CT = false>
 __device__ __forceinline__ void load_stage_a(const ElemArgs& a, long long e, int k, ElemIn& in) {
     const unsigned ue = (unsigned)e;
     in.fl = *at32(a.flag, 4u * ue);
-    in.n = *at32(a.conn, 32u * ue + 4u * (unsigned)k);
+    if (!CT) in.n = *at32(a.conn, 32u * ue + 4u * (unsigned)k);
     in.mt = *at32(a.mat, a.mat_stride * ue);  // (stride 0: one material, every lane reads mat[0] = 0)
     const int kn = EXACT ? k : ref_of_sign(k);  // the node whose force lane k ends up with
     in.fb = (int)(24 * e + 3 * kn);
+}
+
+// Connectivity templates (hakai_conn_plan.hpp): lane k's node is the element's base node plus entry k
+// of the element's offset pattern. Three steps, each a batch apart in k_element_pipe so that none
+// waits: the element's 4-B record (the eight lanes of an element read the same word); the offset,
+// a dependent load from a table of at most 8 KB that stays in the caches; their sum.
+__device__ __forceinline__ int conn_rec(const ElemArgs& a, long long e) {
+    return (int)*at32(a.conn_rec, 4u * (unsigned)e);
+}
+__device__ __forceinline__ int conn_off(const ElemArgs& a, int rec, int k) {
+    const int* pat = reinterpret_cast<const int*>(a.conn_rec + a.nEp);
+    return *at32(pat, 32u * ((unsigned)rec >> a.conn_bits) + 4u * (unsigned)k);
+}
+__device__ __forceinline__ int conn_node(const ElemArgs& a, int rec, int off) {
+    return (int)((unsigned)rec & ((1u << a.conn_bits) - 1u)) + off;
 }
 
 // Gauss-point state accesses: plain, or nontemporal (streamed once per step; keeps the caches for
@@ -1017,8 +1034,17 @@ __device__ __forceinline__ void own_pass(const ElemArgs& a, int4 en, int4 h, lon
 // before computing batch b, so HBM latency hides under the FP64 work even at 2 waves per SIMD.
 // Material tables are staged in LDS (segment searches hit LDS, not L2).
 // TPL: the owner-assembly lists are in template form (compile-time, so neither form pays a branch).
+// CT: connectivity templates (conn_rec, conn_off, conn_node), compile-time for the same reason; fused
+// kernel only. The record is loaded three batches ahead (stage B needs the node a batch ahead), the
+// offset at the top of the next iteration -- the record landed a batch ago, and no store of this
+// iteration is older than the load, so waiting for it later waits for nothing else -- and the two
+// are added at the end of that iteration, behind the batch's arithmetic and summing pass. Two more
+// registers are live across the arithmetic than with conn. The reference-order kernel has none to
+// spare: with the record where conn was and the offset loaded behind the arithmetic (the only place
+// that costs it no register) the wait for the offset also waits for the batch's state stores, and
+// C3 ran 2.3 % slower (profiles/conn_templates_ab.json), so that kernel keeps conn.
 template <bool DO_DELETE, bool STORE_TRIAX, bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS = 0,
-          bool TPL = false>
+          bool TPL = false, bool CT = false>
 __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
     constexpr bool OWN = OS > 0;                 // owner-computed assembly, OS batches per super-batch
     constexpr int kOwnFe = OS * kEPB * kFeStride;  // staged forces per pass (doubles)
@@ -1083,8 +1109,18 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
 #endif
     ElemIn cur, nxt;
     int4 ent_cur = {0, 0, 0, 0}, ent_nxt = {0, 0, 0, 0};
-    load_stage_a<EXACT>(a, elem_of(0), k, cur);
-    load_stage_a<EXACT>(a, elem_of(1), k, nxt);
+    load_stage_a<EXACT, CT>(a, elem_of(0), k, cur);
+    load_stage_a<EXACT, CT>(a, elem_of(1), k, nxt);
+    static_assert(!(CT && EXACT), "connectivity templates: fused kernel only");
+    // (CT, at the top of iteration i: cur.n and nxt.n are nodes, rec_nn is the record of batch i + 2.
+    // The prologue waits for its loads.)
+    int rec_nn = 0;
+    if (CT) {
+        const int r0 = conn_rec(a, elem_of(0)), r1 = conn_rec(a, elem_of(1));
+        cur.n = conn_node(a, r0, conn_off(a, r0, k));
+        nxt.n = conn_node(a, r1, conn_off(a, r1, k));
+        rec_nn = conn_rec(a, elem_of(2));
+    }
     if (!EXACT) load_stage_b<ANY_PLASTIC, NT>(a, elem_of(0), k, cur);
     // (OWN: super-batch of iteration i starts at iteration i - i % OS; its entries are listed under
     // the schedule position of its first batch)
@@ -1101,7 +1137,13 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
     }
     for (long long i = 0; i < count; ++i) {
         ElemIn nn;
-        load_stage_a<EXACT>(a, elem_of(i + 2), k, nn);
+        load_stage_a<EXACT, CT>(a, elem_of(i + 2), k, nn);
+        int off = 0;  // CT: the offset of nn's lane, in flight over this batch
+        if (CT) {
+            nn.n = rec_nn;
+            rec_nn = conn_rec(a, elem_of(i + 3));
+            off = conn_off(a, nn.n, k);
+        }
         if (OWN && TPL) hdr_nn = own_hdr_load(a, sb_of(i + 2));
         // (reference-order mode: its longer arithmetic holds more registers, so nothing of the
         // current batch's nodes or Gauss points is loaded a batch ahead -- only connectivity and
@@ -1136,6 +1178,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_element_pipe(ElemArgs a) {
                 hdr_nxt = hdr_nn;
             }
         }
+        if (CT) nn.n = conn_node(a, nn.n, off);
         cur = nxt;
         nxt = nn;
     }
@@ -1190,37 +1233,44 @@ static void launch_element_w(const ElemArgs& a, bool do_delete, bool store_triax
     }
 }
 
-template <bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS, bool TPL = false>
+template <bool ANY_PLASTIC, bool LDS_MATS, int NT, bool EXACT, int OS, bool TPL = false, bool CT = false>
 static void launch_pipe(const ElemArgs& a, bool do_delete, bool store_triax, unsigned grid, hipStream_t s) {
     const size_t dyn = (OS > 0 ? 24 * (size_t)a.own_slots : 0) + (LDS_MATS ? sizeof(DevMat) * (size_t)a.nmat : 0);
     if (do_delete) {
         if (store_triax)
-            hipLaunchKernelGGL((k_element_pipe<true, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<true, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL, CT>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
         else
-            hipLaunchKernelGGL((k_element_pipe<true, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<true, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL, CT>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
     } else {
         if (store_triax)
-            hipLaunchKernelGGL((k_element_pipe<false, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<false, true, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL, CT>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
         else
-            hipLaunchKernelGGL((k_element_pipe<false, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL>), dim3(grid),
+            hipLaunchKernelGGL((k_element_pipe<false, false, ANY_PLASTIC, LDS_MATS, NT, EXACT, OS, TPL, CT>), dim3(grid),
                                dim3(kBlock), dyn, s, a);
     }
 }
 
-template <bool ANY_PLASTIC, bool LDS_MATS, bool EXACT, int OS, bool TPL = false>
+template <bool ANY_PLASTIC, bool LDS_MATS, bool EXACT, int OS, bool TPL = false, bool CT = false>
 static void launch_pipe_nt(const ElemArgs& a, bool do_delete, bool store_triax, unsigned grid, hipStream_t s) {
     if (a.gp_nt)
-        launch_pipe<ANY_PLASTIC, LDS_MATS, 3, EXACT, OS, TPL>(a, do_delete, store_triax, grid, s);
+        launch_pipe<ANY_PLASTIC, LDS_MATS, 3, EXACT, OS, TPL, CT>(a, do_delete, store_triax, grid, s);
     else
-        launch_pipe<ANY_PLASTIC, LDS_MATS, 0, EXACT, OS, TPL>(a, do_delete, store_triax, grid, s);
+        launch_pipe<ANY_PLASTIC, LDS_MATS, 0, EXACT, OS, TPL, CT>(a, do_delete, store_triax, grid, s);
 }
 
 template <bool ANY_PLASTIC, bool LDS_MATS, bool EXACT>
 static void launch_pipe_os(const ElemArgs& a, bool do_delete, bool store_triax, unsigned grid, hipStream_t s) {
-    if (a.own == 1 && a.own_hdr)
+    // (connectivity templates: instantiated for the fused kernel's owner-assembly template variants
+    // only, the default path -- CT = !EXACT below names no new reference-order instantiation; every
+    // other variant reads the plain array)
+    if (!EXACT && a.own == 1 && a.own_hdr && a.conn_rec)
+        launch_pipe_nt<ANY_PLASTIC, true, EXACT, 1, true, !EXACT>(a, do_delete, store_triax, grid, s);
+    else if (!EXACT && a.own == 2 && a.own_hdr && a.conn_rec)
+        launch_pipe_nt<ANY_PLASTIC, true, EXACT, 2, true, !EXACT>(a, do_delete, store_triax, grid, s);
+    else if (a.own == 1 && a.own_hdr)
         launch_pipe_nt<ANY_PLASTIC, true, EXACT, 1, true>(a, do_delete, store_triax, grid, s);
     else if (a.own == 2 && a.own_hdr)
         launch_pipe_nt<ANY_PLASTIC, true, EXACT, 2, true>(a, do_delete, store_triax, grid, s);
@@ -1255,6 +1305,7 @@ hipError_t launch_element(const ElemArgs& a, bool do_delete, bool store_triax, h
             a.own_slots > own_slot_cap(a.exact != 0, a.own, a.nmat))
             return hipErrorInvalidValue;
         if (a.own_grid <= 0 || a.own_grid > nb) return hipErrorInvalidValue;  // (own_bstart has grid+1 entries)
+        if (a.conn_rec && (a.conn_bits < 0 || a.conn_bits > 31)) return hipErrorInvalidValue;
         if (a.exact)
             launch_pipe_p<true>(a, do_delete, store_triax, (unsigned)a.own_grid, s);
         else

@@ -16,6 +16,12 @@ struct ElemArgs {
     const double* u;       // disp  (after this step's update)
     const double* u_pre;   // disp_pre (= disp of the previous step) -> d_disp = u - u_pre
     const int* conn;       // 8nE, 0-based
+    // Connectivity templates (tuning "conn_templates", hakai_conn_plan.hpp) when conn_rec is set: the
+    // fused kernel's owner-assembly template variants of k_element_pipe read one packed record per
+    // element and the offset table instead of conn. Every other kernel reads conn.
+    const unsigned* conn_rec;  // [nEp] base | pattern << conn_bits, then the table [P][8] of node
+                               // offsets from the base (int32; one array: one pointer in the kernel)
+    int conn_bits;
     int* flag;             // nE: 1 active, 2 deleted in the previous step (fe still live), 0 deleted
     const int* mat;        // nE, 0-based
     unsigned mat_stride;   // bytes between elements' entries of mat: 4, or 0 for a one-material model

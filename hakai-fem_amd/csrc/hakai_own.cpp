@@ -119,6 +119,14 @@ bool own_prepare(hakai_ctx* c) {
     return own_wanted(c);
 }
 
+// Connectivity templates (hakai_conn_plan.hpp): the fused element kernel has the compressed form in
+// its owner-assembly template variants only, so it is in use when the mesh has one, the tuning key is
+// on, the next element step takes owner assembly with its lists in template form, and the arithmetic
+// is the fused kernel's.
+static bool conn_in_use(const hakai_ctx* c) {
+    return c->conn_templates && c->conn_P > 0 && !c->elem_exact && own_wanted(c) && c->own.l.d_hdr.get();
+}
+
 void own_elem_args(const hakai_ctx* c, hk::ElemArgs& ea) {
     const Own::Lists& l = c->own.l;
     ea.own = l.s;
@@ -133,6 +141,10 @@ void own_elem_args(const hakai_ctx* c, hk::ElemArgs& ea) {
     ea.own_q = l.d_q;
     ea.own_rows = l.d_rows;
     ea.own_dump = l.d_dump;
+    if (conn_in_use(c)) {
+        ea.conn_rec = c->d_conn_rec;
+        ea.conn_bits = c->conn_bits;
+    }
 }
 
 int own_tuning(hakai_ctx* c, const char* key, long long value) {
@@ -192,6 +204,8 @@ int own_stat(const hakai_ctx* c, const char* key, int64_t* value) {
     else if (!std::strcmp(key, "own_slots")) *value = built ? l.slots : 0;
     else if (!std::strcmp(key, "own_banded")) *value = built ? l.banded : 0;
     else if (!std::strcmp(key, "own_grid")) *value = built ? l.built_g : 0;
+    else if (!std::strcmp(key, "conn_patterns")) *value = conn_in_use(c) ? c->conn_P : 0;
+    else if (!std::strcmp(key, "conn_bytes")) *value = conn_in_use(c) ? c->conn_bytes : 32 * c->nEp;
     else return fail(HAKAI_ERR_ARG, "unknown stat '%s'", key);
     return 0;
 }

@@ -143,6 +143,7 @@ def lib() -> ctypes.CDLL:
         "hakai_profile_enable": (c_int, [c_void_p, c_int]),
         "hakai_profile_read": (c_int, [c_void_p, c_int, PD, PI64]),
         "hakai_profile_mask": (c_int, [c_void_p, ctypes.c_uint32]),
+        # (keys: include/hakai_hip.h; "conn_templates" 1/0: connectivity as base node + shared offset pattern)
         "hakai_set_tuning": (c_int, [c_void_p, c_char_p, c_int64]),
         "hakai_set_contact": (c_int, [c_void_p, c_int32, PI64]),
         "hakai_set_contact_cp": (c_int, [c_void_p, c_int32, PI64, c_int32, PI32, PI64, PI64]),
@@ -163,6 +164,7 @@ def lib() -> ctypes.CDLL:
                                     PD, PD]),
         "hakai_run_inp": (c_int, [c_char_p, c_char_p, c_int, c_int]),
         "hakai_graph_steps": (c_int, [c_void_p, PI64]),
+        # (keys: include/hakai_hip.h; "conn_patterns" 0 = plain connectivity array in use, "conn_bytes" per launch)
         "hakai_stat": (c_int, [c_void_p, c_char_p, PI64]),
         "hakai_history_enable": (c_int, [c_void_p, c_int32, PI64, PI64, c_int64, c_int64]),
         "hakai_history_disable": (c_int, [c_void_p]),

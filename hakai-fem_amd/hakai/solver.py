@@ -232,7 +232,8 @@ class Solver:
         check(self.L.hakai_set_tuning(self.ctx, key.encode(), int(value)))
 
     def stat(self, key: str) -> int:
-        """Step-loop counter (hakai_stat): graph_steps, own_steps, own_rows, own_entries, own_superbatch, own_slots."""
+        """Step-loop counter (hakai_stat): graph_steps, own_steps, own_rows, own_entries, own_superbatch, own_slots,
+        conn_patterns (0: the element kernel reads the plain connectivity array), conn_bytes."""
         n = I64(0)
         check(self.L.hakai_stat(self.ctx, key.encode(), ctypes.byref(n)))
         return n.value

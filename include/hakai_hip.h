@@ -124,8 +124,10 @@ int hakai_graph_steps(hakai_ctx* ctx, int64_t* n_steps);
  * entries for this mesh), "own_superbatch" (batches of 32 elements per LDS summing pass: 2, or 1
  * for wide meshes), "own_slots" (LDS running sums a block keeps open at most), "own_banded" (1: the
  * blocks walk row bands of a structured wide cross-section), "own_grid" (blocks of that schedule),
- * "own_round2" (summing passes that take a second entry per thread), "exchange_retries" (steps run
- * again after a multi-GPU contact exchange block overflowed). */
+ * "own_round2" (summing passes that take a second entry per thread), "conn_patterns" (offset patterns
+ * of the connectivity templates the element kernel reads; 0: it reads the plain connectivity array),
+ * "conn_bytes" (connectivity bytes the element kernel reads per launch in that form),
+ * "exchange_retries" (steps run again after a multi-GPU contact exchange block overflowed). */
 int hakai_stat(hakai_ctx* ctx, const char* key, int64_t* value);
 int hakai_sync(hakai_ctx* ctx);
 /* Deletions so far (v2/HAKAI_j.jl:733-736): count, and up to cap (step, element 1-based) pairs. */
@@ -196,6 +198,13 @@ int hakai_profile_read(hakai_ctx* ctx, int kernel, double* total_ms, int64_t* la
  *                       -- each distinct summing pass stored once with relative targets, a 16-byte
  *                       header per pass (hakai_stat "own_templates": distinct passes, 0 = plain
  *                       form; "own_entries_stored"); 0: the plain lists; re-planned at the next step;
+ *   "conn_templates"    1 (default): where the mesh has at most 256 distinct patterns of node offsets
+ *                       conn[e][k] - conn[e][0] (a structured or extruded mesh has a handful), the
+ *                       owner-assembly template variants of the fused element kernel read a 4-byte record
+ *                       per element -- base node and pattern id -- and the cached pattern table
+ *                       instead of the 32-byte connectivity row (hakai_stat "conn_patterns",
+ *                       "conn_bytes"); other meshes and kernels read the plain array; 0: the plain
+ *                       array everywhere;
  *   "nodal_padded"      0: CSR force gather instead of the padded [nN][8] table;
  *   "fuse_bc"           1 (default): one GPU, <= 2^18 nodes: the nodal kernel applies the BCs;
  *   "graph"             steps per captured hipGraph (even, default 16; 0 = stream mode);

@@ -4,9 +4,9 @@
 Compiles a HIP source for gfx950 with the Makefile's flags (its -ffp-contract per file) and `-Rpass-analysis=kernel-resource-usage`
 (the compiler's own per-kernel report, no GPU needed) and prints one JSON object. The element
 kernel's template arguments are named (`hk::k_element_pipe<DO_DELETE, STORE_TRIAX, ANY_PLASTIC,
-LDS_MATS, NT, EXACT, OS>`, csrc/hakai_kernels.hip), so the two instantiations the C3 bench times are
-easy to find: fused `<1,0,1,1,3,0,2>` and reference order `<1,0,1,1,3,1,2>` (its owner path; the fe
-fallback is OS = 0).
+LDS_MATS, NT, EXACT, OS, TPL, CT>`, csrc/hakai_kernels.hip), so the two instantiations the C3 bench
+times are easy to find: fused `<1,0,1,1,3,0,2,1,1>` and reference order `<1,0,1,1,3,1,2,1,1>` (its
+owner path with template lists and connectivity templates; the fe fallback is OS = 0).
 
     python tools/kernel_resources.py [--src csrc/hakai_kernels.hip] [--remarks FILE] > out.json
 
@@ -29,7 +29,7 @@ CONTRACT = {"hakai_kernels.hip": "-ffp-contract=on", "hakai_contact.hip": "-ffp-
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
           "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "lds_static_bytes", "Dynamic Stack": "dynamic_stack"}
-PIPE_ARGS = ("DO_DELETE", "STORE_TRIAX", "ANY_PLASTIC", "LDS_MATS", "NT", "EXACT", "OS")
+PIPE_ARGS = ("DO_DELETE", "STORE_TRIAX", "ANY_PLASTIC", "LDS_MATS", "NT", "EXACT", "OS", "TPL", "CT")
 
 
 def parse(text):
@@ -68,10 +68,11 @@ def describe(sym):
     targs = re.findall(r"L([bi])(\d+)E", sym[len("_ZN2hk") + len(m.group(1)) + n:])
     vals = [bool(int(v)) if t == "b" else int(v) for t, v in targs]
     d = {"kernel": name, "template_args": vals}
-    if name == "k_element_pipe" and len(vals) == len(PIPE_ARGS):
-        d["args"] = dict(zip(PIPE_ARGS, vals))
+    if name == "k_element_pipe" and 7 <= len(vals) <= len(PIPE_ARGS):  # (TPL, CT: later additions, default false)
+        d["args"] = dict(zip(PIPE_ARGS, vals + [False] * (len(PIPE_ARGS) - len(vals))))
         d["mode"] = "reference_order" if d["args"]["EXACT"] else "fused"
         d["assembly"] = f"owner OS={d['args']['OS']}" if d["args"]["OS"] else "fe"
+        d["assembly"] += (" tpl" if d["args"]["TPL"] else "") + (" conn_tpl" if d["args"]["CT"] else "")
     return d
 
 
