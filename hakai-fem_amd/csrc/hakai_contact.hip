@@ -690,7 +690,7 @@ __global__ __launch_bounds__(128) void k_ct_tri32(StepIn s, unsigned int* ctl, c
 // allocator (ranges are disjoint; their order is irrelevant) -> scatter -> sum.
 // Block 0 also poisons the step when a buffer overflowed in it (events beyond a shard, candidate
 // triangles beyond their buffer, a truncated multi-GPU mirror block): the nodal, BC, element and
-// interface kernels of this and later steps of the call then write nothing (hakai_kernels.hip,
+// interface kernels of this and later steps of the call then write nothing (hakai_device.hpp,
 // poisoned), so the state stays the last good step's and hakai_step reports the overflow.
 __device__ __forceinline__ void count_body(int bid, int nb, unsigned int* ctl, const unsigned int* evs,
                                            long long shard_cap, const int* ev_nodes, int* cnt, int* touched,

@@ -95,7 +95,7 @@ __host__ __device__ __forceinline__ int box_words(int npairs) { return 12 * npai
 __device__ __forceinline__ bool box_max(int q) { return ((q % 12) / 3) % 2 == 1; }
 
 // A buffer overflowed in step `step`: the first one of a call poisons it from that step on (the
-// nodal, BC, element and interface kernels then write nothing, hakai_kernels.hip poisoned)
+// nodal, BC, element and interface kernels then write nothing, hakai_device.hpp poisoned)
 __device__ __forceinline__ void poison_from(int* poison, int step) {
     if (poison[0] == 0) {
         poison[1] = step;

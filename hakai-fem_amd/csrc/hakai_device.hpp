@@ -127,4 +127,8 @@ __device__ __forceinline__ unsigned xcd_remap_rev(unsigned b, unsigned nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (len - 1 - (b >> 3));
 }
 
+// A contact buffer overflowed earlier in this hakai_step call (hakai_contact.hip, k_ct_count):
+// every state-writing kernel returns at once, so the state stays the last good step's.
+__device__ __forceinline__ bool poisoned(const int* p) { return p && *p; }
+
 }  // namespace hk

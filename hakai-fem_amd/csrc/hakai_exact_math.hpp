@@ -1,5 +1,5 @@
 // hakai_exact_math.hpp -- scalar helpers of the reference-order element kernel (elem_step_exact in
-// hakai_kernels.hip): the correctly rounded divisions, the hardening-segment search and the ductile
+// hakai_elem_exact.hpp): the correctly rounded divisions, the hardening-segment search and the ductile
 // table. One source for the device and for the CPU tests: tests/test_div3.py and
 // tests/test_exact_chains.py compile THIS file with a host compiler (no contraction, fma enabled)
 // and compare it with IEEE division and with the oracle, so an edit here is an edit they see.

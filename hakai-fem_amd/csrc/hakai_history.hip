@@ -72,8 +72,6 @@ struct HistArgs {
     double t;
 };
 
-__device__ __forceinline__ bool hist_poisoned(const int* p) { return p && *p; }
-
 // One binary tree over items pushed in order: an item whose index has k trailing one bits closes
 // k subtrees. `stk` is this thread's column of an LDS array [depth][kHB].
 struct PairTree {
@@ -355,14 +353,14 @@ __device__ __forceinline__ void hist_finish(const HistArgs& h, double* stk, doub
 
 template <int MODE>
 __global__ __launch_bounds__(kHB) void k_history_part(HistArgs h) {
-    if (!h.seed && hist_poisoned(h.na.poison)) return;  // block-uniform
+    if (!h.seed && poisoned(h.na.poison)) return;  // block-uniform
     __shared__ double lds_w[4 * kHMaxS * kHF];
     __shared__ double stk[kHDepthPart * kHB];
     hist_group<MODE>(h, blockIdx.x, lds_w, stk);
 }
 
 __global__ __launch_bounds__(kHB) void k_history_finish(HistArgs h) {
-    if (!h.seed && hist_poisoned(h.na.poison)) return;
+    if (!h.seed && poisoned(h.na.poison)) return;
     __shared__ double stk[kHDepth * kHB];
     __shared__ double red[kHB];
     hist_finish(h, stk, red);
@@ -370,7 +368,7 @@ __global__ __launch_bounds__(kHB) void k_history_finish(HistArgs h) {
 
 template <int MODE>
 __global__ __launch_bounds__(kHB) void k_history_one(HistArgs h) {
-    if (!h.seed && hist_poisoned(h.na.poison)) return;
+    if (!h.seed && poisoned(h.na.poison)) return;
     __shared__ double lds_w[4 * kHMaxS * kHF];
     __shared__ double stk[kHDepth * kHB];
     __shared__ double red[kHB];

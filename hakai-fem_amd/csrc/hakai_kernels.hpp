@@ -119,7 +119,7 @@ struct NodalArgs {
 // LDS running-sum slots one block of the owner-assembly element kernel may hold: what two blocks
 // per CU (80 KB each) leave next to the kernel's static arrays (node area 12.8 KB, force staging
 // 12 KB per batch of a pass, double-buffered, and in reference-order mode the exchange area and
-// the Pusai table, 20 KB; hakai_kernels.hip checks these sizes) and the staged materials; at most
+// the Pusai table, 20 KB; hakai_elem_io.hpp checks these sizes) and the staged materials; at most
 // kOwnSlotsMax (11-bit slot ids in the entry lists).
 inline int own_slot_cap(bool exact, int batches_per_pass, int nmat) {
     // (force staging: 6400 B per batch -- 32 elements x 25 doubles, padded -- two buffers)

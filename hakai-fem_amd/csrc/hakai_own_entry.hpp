@@ -1,5 +1,5 @@
 // hakai_own_entry.hpp -- the 16-byte list entry of owner-computed assembly, stated once. The planner
-// (hakai_own_plan.cpp) packs entries, the element kernel (hakai_kernels.hip own_load, own_lane,
+// (hakai_own_plan.cpp) packs entries, the element kernel (hakai_own_pass.hpp own_load, own_lane,
 // own_entry) and the CPU replay (tools/own_plan_check.cpp) read them, all through this file: no
 // other file holds a shift or a mask of the format. Plain ints, no device types: nothing in here
 // needs hip_runtime.h.

@@ -21,7 +21,7 @@ namespace hk {
 // export entry carries up to 4 contributions of any nodes to consecutive rows); own_ridx lists
 // each node's rows in element order. One 16-B entry per node segment piece (or exported
 // contribution) per super-batch of S = 2 schedule positions (1 when 2 would need more than 512
-// entries), one or two per thread (format: hakai_own_entry.hpp, kernel: hakai_kernels.hip
+// entries), one or two per thread (format: hakai_own_entry.hpp, kernel: hakai_own_pass.hpp
 // own_pass). Slots are allocated per block over the super-batches a sum is open; a schedule needing
 // more than own_slot_cap open sums in one block, or a node with > 8 incidences, does not use the mode.
 //

@@ -1,6 +1,6 @@
 """The exact element kernel's divisions must equal IEEE division bit for bit. The functions under
 test are the kernel's own: this file compiles hakai-fem_amd/csrc/hakai_exact_math.hpp, the header
-hakai_kernels.hip includes, with a host compiler (fma enabled, no contraction) -- there is no copy
+the element kernel (hakai_elem_exact.hpp) includes, with a host compiler (fma enabled, no contraction) -- there is no copy
 of div3 or div_cr here.
   * div3(x) against `x / 3.0` over EVERY binade from 2^-1074 to 2^1023, both signs, 20 000 random
     mantissas per binade and sign, plus +-0, the smallest and largest subnormals and normals,

@@ -1,5 +1,5 @@
 """CPU proof of the reference-order element kernel's rewrites (elem_step_exact in
-hakai-fem_amd/csrc/hakai_kernels.hip), against the oracle's literal cal_stress_hexa
+hakai-fem_amd/csrc/hakai_elem_exact.hpp), against the oracle's literal cal_stress_hexa
 (oracle/hakai_oracle.c stress_one_element, v2/HAKAI_j.jl:1033-1371), BIT FOR BIT.
 
 The kernel computes the reference's expressions with three rewrites that are exact by argument:

@@ -2,7 +2,7 @@
 
 The owner-assembly template variants of the fused element kernel read one packed 4-byte record per
 element (base node and pattern id) and a small table of node offsets instead of the 32-byte
-connectivity row (csrc/hakai_conn_plan.hpp, hakai_kernels.hip conn_rec / conn_off / conn_node). The
+connectivity row (csrc/hakai_conn_plan.hpp, hakai_elem_io.hpp conn_rec / conn_off / conn_node). The
 node ids are the same numbers, so every run here must be BIT-identical, in every downloaded field and
 in the deletion log, to the same run with conn_templates 0. The stat conn_patterns says which form
 ran: the number of patterns, or 0 for the plain array -- key off, a mesh above the pattern cap, or the

@@ -2,7 +2,7 @@
 
 The kernel reads a 16-byte header per super-batch and the shared relative entries instead of the
 plain list, adds the header's bases to the targets and derives the LDS slot as node mod P
-(csrc/hakai_own_plan.hpp, hakai_kernels.hip own_load_tpl / own_entry). The additions and their order
+(csrc/hakai_own_plan.hpp, hakai_own_pass.hpp own_load_tpl / own_entry). The additions and their order
 are the plain form's, so every run here must be BIT-identical, in every downloaded field and in the
 deletion log, to the same run with own_templates 0 and to the fe path (own_assembly 0). Grids are
 forced small so that most sums straddle blocks and the head and tail passes of block runs dominate.

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of gfx950 device assembly: did a change of the sources change a kernel?
 
-    python tools/kernel_asm_diff.py --old OLD... --new NEW... [--only REGEX] [--json OUT] [--lines N]
+    python tools/kernel_asm_diff.py --old OLD... --new NEW... [--old-flags FLAGS] [--new-flags FLAGS]
+                                    [--only REGEX] [--json OUT] [--lines N]
 
 Each OLD / NEW is a device assembly file (.s), a HIP source (compiled to device assembly with the
-Makefile's flags for that file, no GPU needed) or a source tree (every hakai-fem_amd/csrc/*.hip in
+flags its own tree's Makefile gives its object, `make print-flags`, or with --old-flags / --new-flags
+for sources no Makefile knows; no GPU needed) or a source tree (every hakai-fem_amd/csrc/*.hip in
 it, and csrc/hakai_comm.cpp, whose interface kernels hipcc compiles too). The kernels of each side are collected over all its files and matched by base name (`k_...`;
 a template instantiation keeps its mangled arguments), so a kernel may move between files or
 namespaces. Before comparing, mangled symbols are reduced to the base name, basic-block and other
@@ -25,7 +27,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_resources  # noqa: E402  (the Makefile's flags per file)
+import kernel_resources  # noqa: E402  (flags(): the Makefile's flags per object)
 
 SYM = re.compile(r"_Z[A-Za-z0-9_$.]+")
 LOCAL = re.compile(r"\.L[A-Za-z_$]+[0-9_]+")
@@ -98,17 +100,17 @@ def count(body):
     return sum(1 for ln in body if not ln.endswith(":"))
 
 
-def compile_asm(src):
+def compile_asm(src, flags=None):
     with tempfile.TemporaryDirectory() as td:
         o = os.path.join(td, "k.s")
-        p = subprocess.run(["/opt/rocm/bin/hipcc", *kernel_resources.flags(src), "-I", os.path.dirname(src),
+        p = subprocess.run(["/opt/rocm/bin/hipcc", *(flags or kernel_resources.flags(src)), "-I", os.path.dirname(src),
                             "--cuda-device-only", "-S", src, "-o", o], capture_output=True, text=True)
         if p.returncode:
             sys.exit(p.stderr[-4000:])
         return open(o).read()
 
 
-def side(paths):
+def side(paths, flags=None):
     ks = {}
     for p in paths:
         if os.path.isdir(p):
@@ -117,7 +119,7 @@ def side(paths):
         else:
             files = [p]
         for f in files:
-            text = open(f).read() if f.endswith(".s") else compile_asm(f)
+            text = open(f).read() if f.endswith(".s") else compile_asm(f, flags)
             for k, b in kernels(text).items():
                 if k in ks:
                     sys.exit(f"kernel {k} twice on one side ({f})")
@@ -153,11 +155,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
+    ap.add_argument("--old-flags", help="compile flags for the OLD sources in place of their Makefile's")
+    ap.add_argument("--new-flags", help="the same for the NEW sources")
     ap.add_argument("--only", help="regular expression: kernels to compare")
     ap.add_argument("--json", help="write the per-kernel records here")
     ap.add_argument("--lines", type=int, default=12, help="differing lines shown per kernel")
     a = ap.parse_args()
-    recs, bad = compare(side(a.old), side(a.new), a.only, a.lines)
+    recs, bad = compare(side(a.old, (a.old_flags or "").split()), side(a.new, (a.new_flags or "").split()),
+                        a.only, a.lines)
     print(f"{len(recs)} kernels, {bad} not the same")
     if a.json:
         with open(a.json, "w") as f:

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Kernel resource report: VGPRs, AGPRs, SGPRs, spills, static LDS and the compiler's waves per SIMD.
 
-Compiles a HIP source for gfx950 with the Makefile's flags (its -ffp-contract per file) and `-Rpass-analysis=kernel-resource-usage`
-(the compiler's own per-kernel report, no GPU needed) and prints one JSON object. The element
+Compiles a HIP source for gfx950 with the flags its Makefile gives the source's object (`make print-flags
+OBJ=build/NAME.o`, the -ffp-contract setting included; `--flags` for a source no Makefile knows) and
+`-Rpass-analysis=kernel-resource-usage` (the compiler's own per-kernel report, no GPU needed) and prints one JSON object. The element
 kernel's template arguments are named (`hk::k_element_pipe<DO_DELETE, STORE_TRIAX, ANY_PLASTIC,
-LDS_MATS, NT, EXACT, OS, TPL, CT>`, csrc/hakai_kernels.hip), so the two instantiations the C3 bench
+LDS_MATS, NT, EXACT, OS, TPL, CT>`, csrc/hakai_element.hip), so the two instantiations the C3 bench
 times are easy to find: fused `<1,0,1,1,3,0,2,1,1>` and reference order `<1,0,1,1,3,1,2,1,1>` (its
 owner path with template lists and connectivity templates; the fe fallback is OS = 0).
 
-    python tools/kernel_resources.py [--src csrc/hakai_kernels.hip] [--remarks FILE] > out.json
+    python tools/kernel_resources.py [--src csrc/hakai_element.hip] [--flags FLAGS] [--remarks FILE] > out.json
 
 LDS: the static `__shared__` bytes only; the launch adds the owner-sum slots and staged materials
 as dynamic LDS (launch_pipe), which the "lds_dynamic_note" field says. Waves per SIMD are the
@@ -23,9 +24,6 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "hakai-fem_amd")
-FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-munsafe-fp-atomics"]
-CONTRACT = {"hakai_kernels.hip": "-ffp-contract=on", "hakai_contact.hip": "-ffp-contract=off",
-            "hakai_contact_xr.hip": "-ffp-contract=off", "hakai_history.hip": "-ffp-contract=off"}  # as the Makefile
 FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
           "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
           "LDS Size [bytes/block]": "lds_static_bytes", "Dynamic Stack": "dynamic_stack"}
@@ -77,12 +75,20 @@ def describe(sym):
 
 
 def flags(src):
-    return FLAGS + ([CONTRACT[os.path.basename(src)]] if os.path.basename(src) in CONTRACT else [])
+    """The compile flags of the object of `src` (<tree>/hakai-fem_amd/csrc/NAME.hip or .cpp), from the
+    Makefile of the source's own tree."""
+    pkg = os.path.dirname(os.path.dirname(os.path.abspath(src)))
+    obj = "build/" + os.path.splitext(os.path.basename(src))[0] + ".o"
+    p = subprocess.run(["make", "-s", "-C", pkg, "print-flags", "OBJ=" + obj], capture_output=True, text=True)
+    if p.returncode:
+        sys.exit(f"{src}: its Makefile gives no flags for {obj} (pass the flags, or a ready .s file)\n"
+                 + p.stderr[-2000:])
+    return p.stdout.split()
 
 
-def compile_remarks(src):
+def compile_remarks(src, fl=None):
     with tempfile.TemporaryDirectory() as td:
-        p = subprocess.run(["/opt/rocm/bin/hipcc", *flags(src), "-I", os.path.join(PKG, "csrc"), "-c", src,
+        p = subprocess.run(["/opt/rocm/bin/hipcc", *(fl or flags(src)), "-I", os.path.join(PKG, "csrc"), "-c", src,
                             "-o", os.path.join(td, "k.o"), "-Rpass-analysis=kernel-resource-usage"],
                            capture_output=True, text=True)
     if p.returncode:
@@ -92,10 +98,12 @@ def compile_remarks(src):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--src", default=os.path.join(PKG, "csrc", "hakai_kernels.hip"))
+    ap.add_argument("--src", default=os.path.join(PKG, "csrc", "hakai_element.hip"))
+    ap.add_argument("--flags", help="compile flags in place of the Makefile's (a source it does not know)")
     ap.add_argument("--remarks", help="parse this saved remarks file instead of compiling")
     a = ap.parse_args()
-    text = open(a.remarks).read() if a.remarks else compile_remarks(a.src)
+    fl = a.flags.split() if a.flags else (None if a.remarks else flags(a.src))
+    text = open(a.remarks).read() if a.remarks else compile_remarks(a.src, fl)
     ks = parse(text)
     bench = {}
     for r in ks:
@@ -104,7 +112,7 @@ def main():
             bench[f"{r['mode']} {r['assembly']}"] = {k: r.get(k) for k in ("vgprs", "agprs", "sgprs", "vgpr_spill",
                                                                           "sgpr_spill", "scratch_bytes_per_lane",
                                                                           "lds_static_bytes", "waves_per_simd")}
-    print(json.dumps({"source": os.path.relpath(a.src, ROOT), "arch": "gfx950", "flags": flags(a.src),
+    print(json.dumps({"source": os.path.relpath(a.src, ROOT), "arch": "gfx950", "flags": fl,
                       "c3_bench_instantiations": bench,
                       "lds_dynamic_note": "static __shared__ only; launch_pipe adds owner-sum slots and staged "
                                           "materials as dynamic LDS",
