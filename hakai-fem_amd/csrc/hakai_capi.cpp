@@ -10,8 +10,9 @@
 // drop-ins and the kernel-argument builders. hakai_step.cpp is the step driver (one step, graph
 // capture and replay, the overflow rollback, hakai_step and hakai_step_group); hakai_step_view.hpp
 // the host's view of the stepping state, whose member functions alone change it; hakai_own.cpp the
-// run time of owner-computed assembly (hkc::Own); hakai_devmem.hpp the HIP error check and the
-// device buffers every translation unit uses.
+// run time of owner-computed assembly (hkc::Own); hakai_devmem.hpp the HIP error check and
+// hkc::DevBuf, the owner of every device array: the context's are its members (hakai_internal.hpp) and
+// free themselves with it, a function's temporaries are locals.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -57,55 +59,31 @@ int hip_fail(hipError_t e, const char* what) {
 
 }  // namespace hkc
 
-using hkc::dalloc;
-using hkc::dfree;
+using hkc::DevBuf;
 using hkc::fail;
 using hkc::hip_fail;
 using hkc::QSrc;
 
 namespace hkc {
 
+// Releases the previous mesh's arrays before hakai_upload_model allocates the next one's, so a
+// re-upload's peak memory is one mesh. Every array frees itself with the context: one missing from
+// this list is held until the next upload overwrites it or the context goes, never leaked.
 static void free_model(hakai_ctx* c) {
     contact_destroy(c);
     loads_destroy(c);  // sized and validated for the previous mesh
-    dfree(c->d_coord);
-    dfree(c->d_u[0]);
-    dfree(c->d_u[1]);
-    dfree(c->d_mass);
-    dfree(c->d_conn);
+    for (DevBuf<double>* b : {&c->d_coord, &c->d_u[0], &c->d_u[1], &c->d_mass, &c->d_stress, &c->d_strain, &c->d_eqps,
+                              &c->d_yield, &c->d_triax, &c->d_fe, &c->d_qbuf})
+        b->free();
+    for (DevBuf<int>* b : {&c->d_conn, &c->d_flag, &c->d_mat, &c->d_inc_ptr, &c->d_inc, &c->d_inc_row, &c->d_inc8,
+                           &c->d_del_step})
+        b->free();
+    c->d_mats.free();
     c->d_conn_rec.free();
     c->conn_P = 0;
-    dfree(c->d_flag);
-    dfree(c->d_mat);
-    dfree(c->d_mats);
-    dfree(c->d_stress);
-    dfree(c->d_strain);
-    dfree(c->d_eqps);
-    dfree(c->d_yield);
-    dfree(c->d_triax);
-    dfree(c->d_fe);
-    dfree(c->d_inc_ptr);
-    dfree(c->d_inc);
-    dfree(c->d_inc_row);
-    dfree(c->d_inc8);
-    dfree(c->d_del_step);
-    dfree(c->d_qbuf);
-    dfree(c->d_fext);
     own_free(c);
     c->model_ok = false;
     c->state_ok = false;
-}
-
-static void free_bc(hakai_ctx* c) {
-    dfree(c->d_bc_of_node);
-    dfree(c->d_bc_dof);
-    dfree(c->d_bc_grp);
-    dfree(c->d_bc_val);
-    dfree(c->d_amp_n);
-    dfree(c->d_amp_off);
-    dfree(c->d_amp_t);
-    dfree(c->d_amp_v);
-    c->nbc = 0;
 }
 
 // Material constants exactly as hakai() derives them (v2/HAKAI_j.jl:143-160) and readInpFile
@@ -296,14 +274,14 @@ hk::NodalArgs nodal_args(const hakai_ctx* c, double d_time) {
 // Kernel arguments of the boundary conditions of step t, written into disp_new.
 hk::BCArgs bc_args(const hakai_ctx* c, double t, double d_time) {
     hk::BCArgs ba;
-    ba.dof = c->d_bc_dof;
-    ba.grp = c->d_bc_grp;
-    ba.val = c->d_bc_val;
-    ba.n = c->nbc;
-    ba.amp_n = c->d_amp_n;
-    ba.amp_off = c->d_amp_off;
-    ba.amp_t = c->d_amp_t;
-    ba.amp_v = c->d_amp_v;
+    ba.dof = c->bc.d_dof;
+    ba.grp = c->bc.d_grp;
+    ba.val = c->bc.d_val;
+    ba.n = c->bc.n;
+    ba.amp_n = c->bc.d_amp_n;
+    ba.amp_off = c->bc.d_amp_off;
+    ba.amp_t = c->bc.d_amp_t;
+    ba.amp_v = c->bc.d_amp_v;
     ba.out = c->d_u[1 - c->sv.cur];
     ba.ct = t * d_time;
     ba.t_rd = c->gr.trd;
@@ -370,7 +348,14 @@ int hakai_create(hakai_ctx** out, int device) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(HAKAI_ERR_DEVICE, "device %d is %s; libhakai_hip is built for gfx950 only", device,
                     prop.gcnArchName);
-    hakai_ctx* c = new hakai_ctx();
+    // (until the function succeeds: a return on any path below destroys what exists so far)
+    struct Drop {
+        void operator()(hakai_ctx* p) const {
+            if (p->stream) (void)hipStreamDestroy(p->stream);
+            delete p;
+        }
+    };
+    std::unique_ptr<hakai_ctx, Drop> c(new hakai_ctx());
     c->device = device;
     if (const char* v = std::getenv("HAKAI_PIPE_BLOCKS")) c->pipe_blocks = std::atoi(v);
     // HAKAI_GRAPH=n: steps per captured graph (0 = stream mode). rocprofv3 --kernel-trace crashes
@@ -381,18 +366,10 @@ int hakai_create(hakai_ctx** out, int device) {
         c->graph = (g >= 0 && g <= 1024 && !(g & 1)) ? g : 0;
     }
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete c;
-        return hip_fail(e, "hipStreamCreate");
-    }
-    if (dalloc(&c->d_negjac, 1) != hipSuccess || dalloc(&c->d_pusai, 192) != hipSuccess ||
-        dalloc(&c->d_poison, 2) != hipSuccess || hipMemset(c->d_poison, 0, 2 * sizeof(int)) != hipSuccess) {
-        dfree(c->d_negjac);
-        dfree(c->d_pusai);
-        dfree(c->d_poison);
-        delete c;
+    if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
+    if (c->d_negjac.alloc(1) != hipSuccess || c->d_pusai.alloc(192) != hipSuccess ||
+        c->d_poison.alloc(2) != hipSuccess || hipMemset(c->d_poison, 0, 2 * sizeof(int)) != hipSuccess)
         return fail(HAKAI_ERR_DEVICE, "hipMalloc for context bookkeeping failed");
-    }
     {
         double pus[192];
         hkc::pusai_table(pus);
@@ -405,17 +382,11 @@ int hakai_create(hakai_ctx** out, int device) {
                 odd = odd && p[i] == -p[i ^ 1] && p[8 + i] == -p[8 + (i ^ 3)] && p[16 + i] == -p[16 + (i ^ 4)];
             }
         e = odd ? hipMemcpy(c->d_pusai, pus, sizeof pus, hipMemcpyHostToDevice) : hipErrorInvalidValue;
-        if (e != hipSuccess) {
-            dfree(c->d_negjac);
-            dfree(c->d_pusai);
-            dfree(c->d_poison);
-            delete c;
-            return hip_fail(e, "hipMemcpy (Pusai table)");
-        }
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpy (Pusai table)");
     }
     if (const char* v = std::getenv("HAKAI_ELEM_EXACT")) c->elem_exact = std::atoi(v) ? 1 : 0;
     if (const char* v = std::getenv("HAKAI_OWN_ASSEMBLY")) c->own.assembly = std::atoi(v) ? 1 : 0;
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
@@ -425,19 +396,14 @@ int hakai_destroy(hakai_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     prof_harvest(c);
     hkc::graph_free(c);
-    dfree(c->d_tstep);
     hkc::history_destroy(c);
     hkc::stable_dt_destroy(c);
     hkc::mass_scale_destroy(c);
     hkc::comm_destroy(c);
     hkc::free_model(c);
-    hkc::free_bc(c);
-    dfree(c->d_negjac);
-    dfree(c->d_pusai);
-    dfree(c->d_poison);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // (the context's remaining arrays free themselves)
     return 0;
 }
 
@@ -469,7 +435,7 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     hkc::free_model(c);
     // BC tables are sized for the previous mesh (the fused-BC per-dof table has 3nN entries): a new
     // model starts without BCs until hakai_set_bc runs again
-    hkc::free_bc(c);
+    c->bc = {};
     const long long nN = nNode, nE = nElement;
     const long long nEp = ((nE + 31) / 32) * 32;  // whole 32-element batches; padding behaves as deleted
     // host-side conversions
@@ -518,28 +484,28 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     c->nEp = nEp;
     c->ld = 8 * nEp;
     const size_t ld = (size_t)c->ld;
-    HIPCHK(dalloc(&c->d_coord, 3 * (size_t)nN));
-    HIPCHK(dalloc(&c->d_u[0], 3 * (size_t)nN));
-    HIPCHK(dalloc(&c->d_u[1], 3 * (size_t)nN));
-    HIPCHK(dalloc(&c->d_mass, (size_t)nN));
-    HIPCHK(dalloc(&c->d_conn, 8 * (size_t)nEp));
-    HIPCHK(dalloc(&c->d_flag, (size_t)nEp));
-    HIPCHK(dalloc(&c->d_mat, (size_t)nEp));
-    HIPCHK(dalloc(&c->d_del_step, (size_t)nEp + 2));
-    HIPCHK(dalloc(&c->d_mats, (size_t)nMat));
-    HIPCHK(dalloc(&c->d_stress, 6 * ld));
-    HIPCHK(dalloc(&c->d_strain, 6 * ld));
-    HIPCHK(dalloc(&c->d_eqps, ld));
-    HIPCHK(dalloc(&c->d_yield, ld));
-    HIPCHK(dalloc(&c->d_triax, ld));
+    HIPCHK(c->d_coord.alloc(3 * (size_t)nN));
+    HIPCHK(c->d_u[0].alloc(3 * (size_t)nN));
+    HIPCHK(c->d_u[1].alloc(3 * (size_t)nN));
+    HIPCHK(c->d_mass.alloc((size_t)nN));
+    HIPCHK(c->d_conn.alloc(8 * (size_t)nEp));
+    HIPCHK(c->d_flag.alloc((size_t)nEp));
+    HIPCHK(c->d_mat.alloc((size_t)nEp));
+    HIPCHK(c->d_del_step.alloc((size_t)nEp + 2));
+    HIPCHK(c->d_mats.alloc((size_t)nMat));
+    HIPCHK(c->d_stress.alloc(6 * ld));
+    HIPCHK(c->d_strain.alloc(6 * ld));
+    HIPCHK(c->d_eqps.alloc(ld));
+    HIPCHK(c->d_yield.alloc(ld));
+    HIPCHK(c->d_triax.alloc(ld));
     // forces: 24nEp doubles in either layout, then zeros up to 26nEp (padding base 24nEp with
     // component stride up to nEp)
     c->fe_len = 26 * nEp + 8;
-    HIPCHK(dalloc(&c->d_fe, (size_t)c->fe_len));
-    HIPCHK(dalloc(&c->d_inc_ptr, (size_t)nN + 1));
-    HIPCHK(dalloc(&c->d_inc, 8 * (size_t)nE));
-    HIPCHK(dalloc(&c->d_inc_row, 8 * (size_t)nE));
-    HIPCHK(dalloc(&c->d_qbuf, 3 * (size_t)nN));
+    HIPCHK(c->d_fe.alloc((size_t)c->fe_len));
+    HIPCHK(c->d_inc_ptr.alloc((size_t)nN + 1));
+    HIPCHK(c->d_inc.alloc(8 * (size_t)nE));
+    HIPCHK(c->d_inc_row.alloc(8 * (size_t)nE));
+    HIPCHK(c->d_qbuf.alloc(3 * (size_t)nN));
     hipStream_t s = c->stream;
     HIPCHK(hipMemcpyAsync(c->d_coord, coordmat, 3 * nN * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_mass, mass.data(), nN * sizeof(double), hipMemcpyHostToDevice, s));
@@ -562,7 +528,7 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     }
     HIPCHK(hipMemcpyAsync(c->d_mats, c->h_mats.data(), nMat * sizeof(DevMat), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_inc_ptr, ptr.data(), (nN + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    if (maxinc <= 8) HIPCHK(dalloc(&c->d_inc8, 8 * (size_t)nN));  // padded table for the unrolled gather
+    if (maxinc <= 8) HIPCHK(c->d_inc8.alloc(8 * (size_t)nN));  // padded table for the unrolled gather
     HIPCHK(hipStreamSynchronize(s));  // host vectors go out of scope
     c->max_inc = maxinc;
     c->h_ptr = ptr;
@@ -589,7 +555,7 @@ int hakai_set_bc(hakai_ctx* c, const hakai_bc_t* bc) {
     if (!c->model_ok) return fail(HAKAI_ERR_STATE, "set_bc before upload_model");
     HIPCHK(hipSetDevice(c->device));
     (void)hipStreamSynchronize(c->stream);
-    hkc::free_bc(c);
+    c->bc = {};
     const int G = bc->n_groups;
     if (G <= 0) return hkc::history_bc_changed(c);
     // Resolve in-order overwrites: final writer of each dof (v2/HAKAI_j.jl:585-617).
@@ -618,25 +584,25 @@ int hakai_set_bc(hakai_ctx* c, const hakai_bc_t* bc) {
         amp_off[g] = (int)bc->amp_off[g];
         n_amp = std::max<long long>(n_amp, bc->amp_off[g] + bc->amp_n[g]);
     }
-    c->nbc = (int)dof.size();
-    HIPCHK(dalloc(&c->d_bc_dof, dof.size()));
-    HIPCHK(dalloc(&c->d_bc_grp, grp.size()));
-    HIPCHK(dalloc(&c->d_bc_val, val.size()));
-    HIPCHK(dalloc(&c->d_amp_n, (size_t)G));
-    HIPCHK(dalloc(&c->d_amp_off, (size_t)G));
-    HIPCHK(dalloc(&c->d_amp_t, (size_t)n_amp));
-    HIPCHK(dalloc(&c->d_amp_v, (size_t)n_amp));
+    c->bc.n = (int)dof.size();
+    HIPCHK(c->bc.d_dof.alloc(dof.size()));
+    HIPCHK(c->bc.d_grp.alloc(grp.size()));
+    HIPCHK(c->bc.d_val.alloc(val.size()));
+    HIPCHK(c->bc.d_amp_n.alloc((size_t)G));
+    HIPCHK(c->bc.d_amp_off.alloc((size_t)G));
+    HIPCHK(c->bc.d_amp_t.alloc((size_t)n_amp));
+    HIPCHK(c->bc.d_amp_v.alloc((size_t)n_amp));
     hipStream_t s = c->stream;
     if (!dof.empty()) {
-        HIPCHK(hipMemcpyAsync(c->d_bc_dof, dof.data(), dof.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_bc_grp, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_bc_val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->bc.d_dof, dof.data(), dof.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->bc.d_grp, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->bc.d_val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(c->d_amp_n, amp_n.data(), G * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_amp_off, amp_off.data(), G * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->bc.d_amp_n, amp_n.data(), G * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->bc.d_amp_off, amp_off.data(), G * sizeof(int), hipMemcpyHostToDevice, s));
     if (n_amp) {
-        HIPCHK(hipMemcpyAsync(c->d_amp_t, bc->amp_time, n_amp * sizeof(double), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_amp_v, bc->amp_value, n_amp * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->bc.d_amp_t, bc->amp_time, n_amp * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->bc.d_amp_v, bc->amp_value, n_amp * sizeof(double), hipMemcpyHostToDevice, s));
     }
     // per-node table: the first resolved entry of each node (entries are sorted by dof, a node's
     // up-to-3 entries are consecutive) or -1, so the nodal kernel applies the BCs itself
@@ -644,8 +610,8 @@ int hakai_set_bc(hakai_ctx* c, const hakai_bc_t* bc) {
     if (!dof.empty()) {  // (used by k_nodal up to kFuseBcMaxNodes, and by the two-step schedule)
         std::vector<int> of((size_t)c->nN, -1);
         for (size_t i = dof.size(); i-- > 0;) of[(size_t)dof[i] / 3] = (int)i;
-        HIPCHK(dalloc(&c->d_bc_of_node, of.size()));
-        HIPCHK(hipMemcpyAsync(c->d_bc_of_node, of.data(), of.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(c->bc.d_of_node.alloc(of.size()));
+        HIPCHK(hipMemcpyAsync(c->bc.d_of_node, of.data(), of.size() * sizeof(int), hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     return hkc::history_bc_changed(c);
@@ -717,8 +683,8 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
         c->sv.q_uploaded();
     }
     if (st->integ_stress || st->integ_strain) {
-        double* tmp = nullptr;
-        HIPCHK(dalloc(&tmp, 6 * nGP));
+        DevBuf<double> tmp;
+        HIPCHK(tmp.alloc(6 * nGP));
         if (st->integ_stress) {
             HIPCHK(hipMemcpyAsync(tmp, st->integ_stress, 6 * nGP * sizeof(double), hipMemcpyHostToDevice, s));
             HIPCHK(hk::launch_aos_to_soa6(tmp, c->d_stress, (long long)nGP, c->ld, s));
@@ -727,8 +693,7 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
             HIPCHK(hipMemcpyAsync(tmp, st->integ_strain, 6 * nGP * sizeof(double), hipMemcpyHostToDevice, s));
             HIPCHK(hk::launch_aos_to_soa6(tmp, c->d_strain, (long long)nGP, c->ld, s));
         }
-        HIPCHK(hipStreamSynchronize(s));
-        dfree(tmp);
+        HIPCHK(hipStreamSynchronize(s));  // (before tmp goes)
     }
     if (st->integ_yield_stress)
         HIPCHK(hipMemcpyAsync(c->d_yield, st->integ_yield_stress, nGP * sizeof(double), hipMemcpyHostToDevice, s));
@@ -809,21 +774,20 @@ int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
         if (c->sv.q == QSrc::Buf) {
             HIPCHK(hipMemcpyAsync(st->Q, c->d_qbuf, fn * sizeof(double), hipMemcpyDeviceToHost, s));
         } else {
-            double* tmp = nullptr;
-            HIPCHK(dalloc(&tmp, fn));
+            DevBuf<double> tmp;
+            HIPCHK(tmp.alloc(fn));
             if (c->sv.q == QSrc::Own) {  // the last element step's owner-computed sums (fe may be stale)
                 const hkc::OwnSums o = hkc::own_sums(c);
                 HIPCHK(hk::launch_own_q(o.q, o.rp, o.ridx, o.rows, tmp, c->nN, s));
             } else
                 HIPCHK(hk::launch_gather_q(c->d_inc_ptr, c->d_inc, c->d_fe, tmp, c->nN, s));
             HIPCHK(hipMemcpyAsync(st->Q, tmp, fn * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            dfree(tmp);
+            HIPCHK(hipStreamSynchronize(s));  // (before tmp goes)
         }
     }
     if (st->integ_stress || st->integ_strain) {
-        double* tmp = nullptr;
-        HIPCHK(dalloc(&tmp, 6 * nGP));
+        DevBuf<double> tmp;
+        HIPCHK(tmp.alloc(6 * nGP));
         if (st->integ_stress) {
             HIPCHK(hk::launch_soa_to_aos6(c->d_stress, tmp, (long long)nGP, c->ld, s));
             HIPCHK(hipMemcpyAsync(st->integ_stress, tmp, 6 * nGP * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -834,7 +798,6 @@ int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
             HIPCHK(hipMemcpyAsync(st->integ_strain, tmp, 6 * nGP * sizeof(double), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
         }
-        dfree(tmp);
     }
     if (st->integ_yield_stress)
         HIPCHK(hipMemcpyAsync(st->integ_yield_stress, c->d_yield, nGP * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -859,6 +822,7 @@ int hakai_download_state(hakai_ctx* c, hakai_state_t* st) {
 int hakai_stat(hakai_ctx* c, const char* key, int64_t* value) {
     if (!c || !key || !value) return fail(HAKAI_ERR_ARG, "null");
     if (!std::strcmp(key, "graph_steps")) *value = c->graph_steps;
+    else if (!std::strcmp(key, "device_buffers")) *value = hkc::g_dev_live.load();
     else if (!std::strcmp(key, "exchange_retries")) *value = c->exchange_retries;
     else if (!std::strncmp(key, "own_", 4) || !std::strncmp(key, "conn_", 5)) return hkc::own_stat(c, key, value);
     else return fail(HAKAI_ERR_ARG, "unknown stat '%s'", key);
@@ -930,7 +894,7 @@ int hakai_set_tuning(hakai_ctx* c, const char* key, int64_t value) {
     }
     if (!std::strcmp(key, "nodal_padded")) {
         if (!value) {
-            dfree(c->d_inc8);
+            c->d_inc8.free();
             return 0;
         }
         return c->d_inc8 ? 0 : fail(HAKAI_ERR_STATE, "padded incidence table unavailable (>8 incidences)");
@@ -985,12 +949,12 @@ int hakai_node_stress_strain(hakai_ctx* c, double* node_stress, double* node_str
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t nN = (size_t)c->nN;
-    double *ns = nullptr, *nn = nullptr, *ne = nullptr, *nm = nullptr, *nt = nullptr;
-    HIPCHK(dalloc(&ns, 6 * nN));
-    HIPCHK(dalloc(&nn, 6 * nN));
-    HIPCHK(dalloc(&ne, nN));
-    HIPCHK(dalloc(&nm, nN));
-    HIPCHK(dalloc(&nt, nN));
+    DevBuf<double> ns, nn, ne, nm, nt;
+    HIPCHK(ns.alloc(6 * nN));
+    HIPCHK(nn.alloc(6 * nN));
+    HIPCHK(ne.alloc(nN));
+    HIPCHK(nm.alloc(nN));
+    HIPCHK(nt.alloc(nN));
     HIPCHK(hk::launch_node_average(c->d_inc_ptr, c->d_inc_row, c->d_stress, c->d_strain, c->d_eqps, c->d_triax, c->ld,
                                    c->nN, ns, nn, ne, nm, nt, s));
     if (node_stress) HIPCHK(hipMemcpyAsync(node_stress, ns, 6 * nN * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -999,11 +963,6 @@ int hakai_node_stress_strain(hakai_ctx* c, double* node_stress, double* node_str
     if (node_mises) HIPCHK(hipMemcpyAsync(node_mises, nm, nN * sizeof(double), hipMemcpyDeviceToHost, s));
     if (node_triax) HIPCHK(hipMemcpyAsync(node_triax, nt, nN * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    dfree(ns);
-    dfree(nn);
-    dfree(ne);
-    dfree(nm);
-    dfree(nt);
     return 0;
 }
 
@@ -1066,8 +1025,8 @@ int hakai_stress_hexa(int device, int64_t nNode, int64_t nElement, double* Qe, d
     r = hakai_upload_state(c, &st);
     if (r) return r;
     hipStream_t s = c->stream;
-    double* d_vol = nullptr;
-    HIPCHK(dalloc(&d_vol, (size_t)c->nEp));
+    DevBuf<double> d_vol;
+    HIPCHK(d_vol.alloc((size_t)c->nEp));
     HIPCHK(hipMemsetAsync(c->d_fe, 0, 24 * (size_t)nElement * sizeof(double), s));
     hk::ElemArgs ea = hkc::elem_args(c, c->sv.cur);
     ea.vol = d_vol;
@@ -1077,7 +1036,6 @@ int hakai_stress_hexa(int device, int64_t nNode, int64_t nElement, double* Qe, d
     HIPCHK(hipMemcpyAsync(fe.data(), c->d_fe, fe.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(vol.data(), d_vol, vol.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    dfree(d_vol);
     hakai_state_t out;
     std::memset(&out, 0, sizeof out);
     out.integ_stress = integ_stress;
@@ -1101,14 +1059,12 @@ int hakai_triax_stress(int device, int64_t nGP, const double* integ_stress, doub
         return fail(HAKAI_ERR_DEVICE, "no HIP device %d: no CPU fallback", device);
     HIPCHK(hipSetDevice(device));
     if (nGP == 0) return 0;
-    double *st = nullptr, *tx = nullptr;
-    HIPCHK(dalloc(&st, 6 * (size_t)nGP));
-    HIPCHK(dalloc(&tx, (size_t)nGP));
+    DevBuf<double> st, tx;
+    HIPCHK(st.alloc(6 * (size_t)nGP));
+    HIPCHK(tx.alloc((size_t)nGP));
     HIPCHK(hipMemcpy(st, integ_stress, 6 * nGP * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hk::launch_triax_aos(st, tx, nGP, 0));
     HIPCHK(hipMemcpy(integ_triax_stress, tx, nGP * sizeof(double), hipMemcpyDeviceToHost));
-    dfree(st);
-    dfree(tx);
     return 0;
 }
 

@@ -39,13 +39,12 @@ struct Comm {
     hipEvent_t ev_packed[2] = {nullptr, nullptr}, ev_done = nullptr;
     int nslot = 0;
     int n_up = 0, n_dn = 0;          // up: this rank is the lower side (neighbour rank+1); dn: upper side
-    int* d_up = nullptr;             // local node ids
-    int* d_dn = nullptr;
-    double* d_up_sendP[2] = {nullptr, nullptr};  // [n_up][3]
-    double* d_up_recvC = nullptr;                // [n_up][nslot][3]
-    double* d_dn_sendC[2] = {nullptr, nullptr};  // [n_dn][nslot][3]
-    double* d_dn_recvP = nullptr;                // [n_dn][3]
-    double* d_saved = nullptr;                   // u_pre of interface nodes [n_up+n_dn][3]
+    DevBuf<int> d_up, d_dn;          // local node ids
+    DevBuf<double> d_up_sendP[2];    // [n_up][3]
+    DevBuf<double> d_up_recvC;       // [n_up][nslot][3]
+    DevBuf<double> d_dn_sendC[2];    // [n_dn][nslot][3]
+    DevBuf<double> d_dn_recvP;       // [n_dn][3]
+    DevBuf<double> d_saved;          // u_pre of interface nodes [n_up+n_dn][3]
     std::vector<int> h_dn;                       // host copy of d_dn (owner-computed assembly, history)
     std::vector<int> h_up;                       // host copy of d_up (history: the nodes whose Q the fix forms)
     bool iface_set = false;                      // hakai_set_interface has run (an empty interface counts)
@@ -66,8 +65,6 @@ static std::map<long long, LocalGroup*> g_groups;
 
 }  // namespace hkc
 
-using hkc::dalloc;
-using hkc::dfree;
 using hkc::fail;
 using hkc::hip_fail;
 
@@ -228,16 +225,18 @@ __global__ void k_fix_own(const int* up, int n_up, const int* dn, int n_dn, cons
     }
 }
 
+// Releases the previous interface's arrays before the next one's are allocated (an array missing
+// here is held until then or until the communicator goes, never leaked).
 void free_iface(hkc::Comm* m) {
-    dfree(m->d_up);
-    dfree(m->d_dn);
+    m->d_up.free();
+    m->d_dn.free();
     for (int p = 0; p < 2; ++p) {
-        dfree(m->d_up_sendP[p]);
-        dfree(m->d_dn_sendC[p]);
+        m->d_up_sendP[p].free();
+        m->d_dn_sendC[p].free();
     }
-    dfree(m->d_up_recvC);
-    dfree(m->d_dn_recvP);
-    dfree(m->d_saved);
+    m->d_up_recvC.free();
+    m->d_dn_recvP.free();
+    m->d_saved.free();
     m->n_up = m->n_dn = 0;
     m->pending = false;
 }
@@ -628,13 +627,12 @@ int hakai_set_interface(hakai_ctx* c, int64_t n_shared, const int64_t* local_nod
     int nslot = 0;
     for (int n : dn) nslot = std::max(nslot, ptr[n + 1] - ptr[n]);
     if (m->mode == 0) {
-        int* d_ns = nullptr;
-        HIPCHK(dalloc(&d_ns, 1));
+        hkc::DevBuf<int> d_ns;
+        HIPCHK(d_ns.alloc(1));
         HIPCHK(hipMemcpy(d_ns, &nslot, sizeof(int), hipMemcpyHostToDevice));
         NCCLCHK(ncclAllReduce(d_ns, d_ns, 1, ncclInt32, ncclMax, m->nc, m->cs));
         HIPCHK(hipStreamSynchronize(m->cs));
         HIPCHK(hipMemcpy(&nslot, d_ns, sizeof(int), hipMemcpyDeviceToHost));
-        dfree(d_ns);
     } else {
         if (nslot > 8) return fail(HAKAI_ERR_ARG, "local group: node with %d incidences on the upper side", nslot);
         nslot = 8;
@@ -646,15 +644,15 @@ int hakai_set_interface(hakai_ctx* c, int64_t n_shared, const int64_t* local_nod
     m->h_up = up;
     m->iface_set = true;
     hkc::own_invalidate(c);  // owner-assembly lists export every dn node's contributions: rebuilt
-    HIPCHK(dalloc(&m->d_up, up.size()));
-    HIPCHK(dalloc(&m->d_dn, dn.size()));
+    HIPCHK(m->d_up.alloc(up.size()));
+    HIPCHK(m->d_dn.alloc(dn.size()));
     for (int p = 0; p < 2; ++p) {
-        HIPCHK(dalloc(&m->d_up_sendP[p], 3 * up.size()));
-        HIPCHK(dalloc(&m->d_dn_sendC[p], 3 * (size_t)nslot * dn.size()));
+        HIPCHK(m->d_up_sendP[p].alloc(3 * up.size()));
+        HIPCHK(m->d_dn_sendC[p].alloc(3 * (size_t)nslot * dn.size()));
     }
-    HIPCHK(dalloc(&m->d_up_recvC, 3 * (size_t)nslot * up.size()));
-    HIPCHK(dalloc(&m->d_dn_recvP, 3 * dn.size()));
-    HIPCHK(dalloc(&m->d_saved, 3 * (up.size() + dn.size())));
+    HIPCHK(m->d_up_recvC.alloc(3 * (size_t)nslot * up.size()));
+    HIPCHK(m->d_dn_recvP.alloc(3 * dn.size()));
+    HIPCHK(m->d_saved.alloc(3 * (up.size() + dn.size())));
     if (!up.empty()) HIPCHK(hipMemcpy(m->d_up, up.data(), up.size() * sizeof(int), hipMemcpyHostToDevice));
     if (!dn.empty()) HIPCHK(hipMemcpy(m->d_dn, dn.data(), dn.size() * sizeof(int), hipMemcpyHostToDevice));
     m->pending = false;

@@ -1,26 +1,21 @@
 // hakai_devmem.hpp -- what every host translation unit of libhakai_hip.so uses around device memory:
-// the HIP error check, raw allocation helpers and the owning device buffer.
+// the HIP error check and hkc::DevBuf, the one owner of device memory. Every device allocation of the
+// library is a DevBuf, a member of the state that owns it or a local, so a return on any path frees
+// it; this file alone calls the runtime's allocator. A raw device pointer elsewhere is a view of a
+// DevBuf that some state owns, and is commented as one.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <vector>
 
 namespace hkc {
 
 int hip_fail(hipError_t e, const char* what);  // hakai_capi.cpp: sets hakai_last_error
 
-template <class T>
-hipError_t dalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc((void**)p, n * sizeof(T));
-}
-
-template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
+// Device arrays the process holds now (hakai_stat "device_buffers"): one per successful alloc, one
+// less per free of a held array; a move changes nothing.
+inline std::atomic<long long> g_dev_live{0};
 
 // A device array that frees itself: move-only, converts to its pointer at launch sites.
 template <class T>
@@ -40,7 +35,10 @@ class DevBuf {
     }
     ~DevBuf() { free(); }
     void free() {
-        if (p_) (void)hipFree((void*)p_);
+        if (p_) {
+            (void)hipFree((void*)p_);
+            g_dev_live.fetch_sub(1, std::memory_order_relaxed);
+        }
         p_ = nullptr;
     }
     // n elements (at least one), uninitialised; a held array is freed first
@@ -48,7 +46,13 @@ class DevBuf {
         free();
         const hipError_t e = hipMalloc((void**)&p_, (n ? n : 1) * sizeof(T));
         if (e != hipSuccess) p_ = nullptr;
+        else g_dev_live.fetch_add(1, std::memory_order_relaxed);
         return e;
+    }
+    // n elements (at least one), zeroed on stream s
+    hipError_t alloc_zero(size_t n, hipStream_t s) {
+        const hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemsetAsync(p_, 0, (n ? n : 1) * sizeof(T), s);
     }
     hipError_t upload(const std::vector<T>& v, hipStream_t s) {
         const hipError_t e = alloc(v.size());

@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../include/hakai_hip.h"
@@ -417,28 +418,20 @@ struct History {
     long long stride = 1, cap = 1;
     long long nchunks = 0, ngroups = 0;
     bool need_seed = true;
-    double* d_du_prev = nullptr;
-    unsigned short* d_set = nullptr;
-    unsigned char* d_presc = nullptr;
-    double* d_acc = nullptr;
-    double* d_ke = nullptr;
-    double* d_ring = nullptr;
-    unsigned long long* d_count = nullptr;
-    double* d_gp = nullptr;
+    DevBuf<double> d_du_prev;
+    DevBuf<unsigned short> d_set;
+    DevBuf<unsigned char> d_presc;
+    DevBuf<double> d_acc, d_ke, d_ring;
+    DevBuf<unsigned long long> d_count;
+    DevBuf<double> d_gp;
     int n_up = 0;                // a rank: its nodes shared with the rank above, ascending, and their
-    int* d_up_node = nullptr;    // positions in the exchange buffers (hist_q_up)
-    int* d_up_slot = nullptr;
-    void free() {
-        void* p[] = {d_du_prev, d_set, d_presc, d_acc, d_ke, d_ring, d_count, d_gp, d_up_node, d_up_slot};
-        for (void* q : p)
-            if (q) (void)hipFree(q);
-    }
+    DevBuf<int> d_up_node;       // positions in the exchange buffers (hist_q_up)
+    DevBuf<int> d_up_slot;
 };
 
 void history_destroy(hakai_ctx* c) {
     if (!c->hist) return;
     (void)hipStreamSynchronize(c->stream);
-    c->hist->free();
     delete c->hist;
     c->hist = nullptr;
 }
@@ -459,8 +452,8 @@ int history_restart(hakai_ctx* c) {
 int history_bc_changed(hakai_ctx* c) {
     History* H = c->hist;
     if (!H) return 0;
-    std::vector<int> dof((size_t)c->nbc);
-    if (c->nbc > 0) HIPCHK(hipMemcpy(dof.data(), c->d_bc_dof, dof.size() * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int> dof((size_t)c->bc.n);
+    if (c->bc.n > 0) HIPCHK(hipMemcpy(dof.data(), c->bc.d_dof, dof.size() * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<unsigned char> pm((size_t)c->nN, 0);
     for (int d : dof) pm[(size_t)d / 3] |= (unsigned char)(1u << (d % 3));
     if (const std::vector<int>* up = comm_up_nodes(c))  // a rank: the nodes whose Q the interface fix forms
@@ -574,7 +567,7 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
     HIPCHK(hipSetDevice(c->device));
     hkc::graph_invalidate(c);  // the captured steps change
     hkc::history_destroy(c);
-    hkc::History* H = new hkc::History();
+    std::unique_ptr<hkc::History> H(new hkc::History());
     H->n_up = (int)up_node.size();
     H->n_sets = n_sets;
     H->stride = stride;
@@ -582,33 +575,24 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
     H->nchunks = (c->nN + hk::kHB - 1) / hk::kHB;
     H->ngroups = (H->nchunks + hk::kHGroup - 1) / hk::kHGroup;
     const size_t nN = (size_t)c->nN, S16 = 16 * (size_t)S;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, c->stream);
-    };
-    alloc((void**)&H->d_du_prev, 3 * nN * sizeof(double));
-    alloc((void**)&H->d_set, nN * sizeof(unsigned short));
-    alloc((void**)&H->d_presc, nN);
-    alloc((void**)&H->d_acc, 3 * S * sizeof(double));
-    alloc((void**)&H->d_ke, S * sizeof(double));
-    alloc((void**)&H->d_ring, (size_t)capacity * (1 + S16) * sizeof(double));
-    alloc((void**)&H->d_count, sizeof(unsigned long long));
-    alloc((void**)&H->d_gp, (size_t)H->ngroups * S16 * sizeof(double));
+    hipStream_t st = c->stream;
+    HIPCHK(H->d_du_prev.alloc_zero(3 * nN, st));
+    HIPCHK(H->d_set.alloc_zero(nN, st));
+    HIPCHK(H->d_presc.alloc_zero(nN, st));
+    HIPCHK(H->d_acc.alloc_zero(3 * (size_t)S, st));
+    HIPCHK(H->d_ke.alloc_zero((size_t)S, st));
+    HIPCHK(H->d_ring.alloc_zero((size_t)capacity * (1 + S16), st));
+    HIPCHK(H->d_count.alloc_zero(1, st));
+    HIPCHK(H->d_gp.alloc_zero((size_t)H->ngroups * S16, st));
     if (H->n_up > 0) {
-        alloc((void**)&H->d_up_node, up_node.size() * sizeof(int));
-        alloc((void**)&H->d_up_slot, up_slot.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpyAsync(H->d_up_node, up_node.data(), up_node.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(H->d_up_slot, up_slot.data(), up_slot.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+        HIPCHK(H->d_up_node.alloc_zero(up_node.size(), st));
+        HIPCHK(H->d_up_slot.alloc_zero(up_slot.size(), st));
+        HIPCHK(hipMemcpyAsync(H->d_up_node, up_node.data(), up_node.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(H->d_up_slot, up_slot.data(), up_slot.size() * sizeof(int), hipMemcpyHostToDevice, st));
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(H->d_set, set.data(), nN * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        H->free();
-        delete H;
-        return hip_fail(e, "history_enable: device buffers");
-    }
-    c->hist = H;
+    HIPCHK(hipMemcpyAsync(H->d_set, set.data(), nN * sizeof(unsigned short), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->hist = H.release();
     if (int r = hkc::history_bc_changed(c)) {
         hkc::history_destroy(c);
         return r;

@@ -40,11 +40,13 @@ struct hakai_ctx {
     hipStream_t stream = nullptr;
     // model
     long long nN = 0, nE = 0, nEp = 0, ld = 0;
-    double* d_coord = nullptr;
-    double* d_u[2] = {nullptr, nullptr};  // d_u[sv.cur] = disp, d_u[1-sv.cur] = disp_pre
+    // Device memory: every array below is a hkc::DevBuf that this context owns (hakai_devmem.hpp); the
+    // two raw pointers, d_fext and d_ftot, are views of arrays that another state owns.
+    hkc::DevBuf<double> d_coord;
+    hkc::DevBuf<double> d_u[2];           // d_u[sv.cur] = disp, d_u[1-sv.cur] = disp_pre
     hkc::StepView sv;            // the host's view of the stepping state (hakai_step_view.hpp)
-    double* d_mass = nullptr;
-    int* d_conn = nullptr;
+    hkc::DevBuf<double> d_mass;
+    hkc::DevBuf<int> d_conn;
     // connectivity templates (hakai_conn_plan.hpp), planned by hakai_upload_model: the element
     // kernel's packed records [nEp] followed by the offset table [conn_P][8]; conn_P 0: the mesh has no
     // compressed form
@@ -52,21 +54,16 @@ struct hakai_ctx {
     int conn_P = 0, conn_bits = 0;
     long long conn_bytes = 0;    // connectivity bytes per launch of the compressed form
     int conn_templates = 1;      // tuning "conn_templates": use the compressed form where it exists
-    int* d_flag = nullptr;
-    int* d_mat = nullptr;
-    hk::DevMat* d_mats = nullptr;
+    hkc::DevBuf<int> d_flag;
+    hkc::DevBuf<int> d_mat;
+    hkc::DevBuf<hk::DevMat> d_mats;
     std::vector<hk::DevMat> h_mats;
     bool has_ductile = false;
-    double* d_stress = nullptr;
-    double* d_strain = nullptr;
-    double* d_eqps = nullptr;
-    double* d_yield = nullptr;
-    double* d_triax = nullptr;
-    double* d_fe = nullptr;
-    int* d_inc_ptr = nullptr;
-    int* d_inc = nullptr;        // CSR incidences as force base offsets of the active layout
-    int* d_inc_row = nullptr;    // the same incidences as (8e+k), for element-indexed data
-    int* d_inc8 = nullptr;       // padded incidence table, null if a node has > 8 incidences
+    hkc::DevBuf<double> d_stress, d_strain, d_eqps, d_yield, d_triax, d_fe;
+    hkc::DevBuf<int> d_inc_ptr;
+    hkc::DevBuf<int> d_inc;      // CSR incidences as force base offsets of the active layout
+    hkc::DevBuf<int> d_inc_row;  // the same incidences as (8e+k), for element-indexed data
+    hkc::DevBuf<int> d_inc8;     // padded incidence table, null if a node has > 8 incidences
     // Element forces [nEp][8][3] (= the reference's Qe column order), row (e, k) at base 24e + 3k;
     // d_inc / d_inc8 hold the bases, and base 24nEp is an all-zero row (padding).
     long long fe_len = 0;        // doubles allocated for fe
@@ -80,28 +77,27 @@ struct hakai_ctx {
     int group_serial = 0;        // tuning "group_serial" (rank 0 of a hakai_step_group): drain every rank's
                                  // phase before the next rank's (per-rank timings without the ranks
                                  // sharing the one GPU)
-    double* d_pusai = nullptr;   // cal_Pusai_hexa table for the exact element kernel (192 doubles)
+    hkc::DevBuf<double> d_pusai; // cal_Pusai_hexa table for the exact element kernel (192 doubles)
     int nmat = 0;
     long long elem_offset = 0;   // global id of local element 0
-    // bc
-    int nbc = 0;
-    int* d_bc_dof = nullptr;
-    int* d_bc_grp = nullptr;
-    double* d_bc_val = nullptr;
-    int* d_amp_n = nullptr;
-    int* d_amp_off = nullptr;
-    double* d_amp_t = nullptr;
-    double* d_amp_v = nullptr;
-    int* d_bc_of_node = nullptr; // [nN] first resolved BC entry of each node (-1 none)
+    // bc: the resolved tables of hakai_set_bc, sized for the model; `bc = {}` drops them
+    struct BcTables {
+        int n = 0;
+        hkc::DevBuf<int> d_dof, d_grp;
+        hkc::DevBuf<double> d_val;
+        hkc::DevBuf<int> d_amp_n, d_amp_off;
+        hkc::DevBuf<double> d_amp_t, d_amp_v;
+        hkc::DevBuf<int> d_of_node;  // [nN] first resolved BC entry of each node (-1 none)
+    } bc;
     int fuse_bc = 1;             // tuning "fuse_bc": the nodal kernel applies the BCs (one GPU)
     // state extras
-    double* d_qbuf = nullptr;    // the uploaded Q (sv.q == QSrc::Buf: the next nodal update reads it)
+    hkc::DevBuf<double> d_qbuf;  // the uploaded Q (sv.q == QSrc::Buf: the next nodal update reads it)
     std::vector<double> h_velo0;  // velo as uploaded / set by IC, valid until the first step
     double last_dt = 0.0;
-    int* d_del_step = nullptr;   // [nEp+2] deletion step per element (0 = never), [nEp] dump slot,
+    hkc::DevBuf<int> d_del_step; // [nEp+2] deletion step per element (0 = never), [nEp] dump slot,
                                  // [nEp+1] last step in which any element was deleted
-    unsigned long long* d_negjac = nullptr;
-    int* d_poison = nullptr;     // [2]: contact buffer overflow in this call (flag, step); see ElemArgs
+    hkc::DevBuf<unsigned long long> d_negjac;
+    hkc::DevBuf<int> d_poison;   // [2]: contact buffer overflow in this call (flag, step); see ElemArgs
     long long poison_step = -1;  // the step a contact overflow poisoned in the last failed call
     long long exchange_retries = 0;  // steps run again after a multi-GPU contact exchange overflow
     bool any_plastic = false;
@@ -112,7 +108,8 @@ struct hakai_ctx {
     std::vector<int> h_conn;      // 8nE, 0-based
     std::vector<int> h_mat;       // nE, 0-based
     std::vector<double> h_young;  // per material
-    // external force (contact) -- null until contact is enabled (the contact state owns the array)
+    // external force (contact) -- null until contact is enabled; a non-owning view of
+    // Contact::d_fext, set and cleared by the contact state
     double* d_fext = nullptr;
     hkc::Contact* contact = nullptr;
     // profiling
@@ -125,7 +122,7 @@ struct hakai_ctx {
     // graph mode (hakai_step): `graph` steps (even) captured in one hipGraph per starting parity
     // (cur), plus a 2-step graph for the tail; the step number is read from a device counter
     // instead of kernel arguments. Slot [g][p]: g 0 = `graph` steps, 1 = 2 steps; p = parity.
-    double* d_tstep = nullptr;         // [2] counter slots (slot 1-cur: previous step's number)
+    hkc::DevBuf<double> d_tstep;       // [2] counter slots (slot 1-cur: previous step's number)
     struct StepGraphs {
         const double* trd = nullptr;   // non-null while a step is captured: its counter slot
         hipGraphExec_t exec[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -151,8 +148,8 @@ struct hakai_ctx {
     // uploaded nodal mass, null until the first call (d_mass then holds the scaled mass)
     hkc::MassScale* msc = nullptr;
     // external loads and rigid walls (hakai_set_loads, hakai_set_walls; hakai_loads.hpp): null without
-    // both. d_ftot [3nN] is the step's total external force, contact plus loads plus walls (owned by
-    // that state)
+    // both. d_ftot [3nN] is the step's total external force, contact plus loads plus walls: a
+    // non-owning view of Loads::ftot, set and cleared by that state
     hkc::Loads* loads = nullptr;
     double* d_ftot = nullptr;
 };

@@ -28,7 +28,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/hakai_hip.h"
@@ -222,21 +224,10 @@ void launch_cl(const LoadArgs& a, bool cl, bool gr, bool pr, int wl, unsigned gr
         launch_gr<FC, false>(a, gr, pr, wl, grid, s);
 }
 
+// A planned array on its way to the device; an empty one allocates nothing and stays a null pointer.
 template <class T>
-hipError_t upload(std::vector<void*>& owned, const T** d, const std::vector<T>& h, hipStream_t s) {
-    *d = nullptr;
-    if (h.empty()) return hipSuccess;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, h.size() * sizeof(T));
-    if (e != hipSuccess) return e;
-    owned.push_back(p);
-    *d = (const T*)p;
-    return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
-}
-
-void free_all(std::vector<void*>& owned) {
-    for (void* p : owned) (void)hipFree(p);
-    owned.clear();
+hipError_t upload(hkc::DevBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
+    return h.empty() ? hipSuccess : d.upload(h, s);
 }
 
 }  // namespace
@@ -246,51 +237,60 @@ namespace hkc {
 // Device state of the external force: the loads' plan (hakai_loads_plan.hpp), the walls' plan
 // (hakai_walls_plan.hpp) -- either may be absent, not both -- and the total external force of the step.
 struct Loads {
-    void* ftot = nullptr;                // [3nN], c->d_ftot
-    std::vector<void*> owned_l, owned_w; // the device allocations of the loads / of the walls
-    LoadArgs a;                          // both plans' pointers; the per-step fields are filled at launch
+    DevBuf<double> ftot;                 // [3nN], c->d_ftot
+    struct LoadBufs {                    // hakai_set_loads' plan (LoadArgs has the fields' meaning)
+        DevBuf<int> amp_n, amp_off;
+        DevBuf<double> amp_t, amp_v;
+        DevBuf<int> cl_ptr, cl_comp, cl_amp;
+        DevBuf<double> cl_val, g_acc;
+        DevBuf<int> g_amp, pr_ptr, pr_ent, pr_elem, pr_code, pr_amp;
+        DevBuf<double> pr_val;
+    } lb;
+    struct WallBufs {                    // hakai_set_walls' plan
+        DevBuf<int> amp_n, amp_off;
+        DevBuf<double> amp_t, amp_v, tab;
+        DevBuf<int> amp;
+        DevBuf<unsigned> mask;
+    } wb;
+    int n_grav = 0, n_wall = 0;
     bool cl = false, gr = false, pr = false;
     int wl = 0;                          // 0 no wall, 1 every wall takes every node, 2 mask
     bool has_loads() const { return cl || gr || pr; }
 };
 
-static void loads_free(Loads* L) {
-    if (!L) return;
-    free_all(L->owned_l);
-    free_all(L->owned_w);
-    if (L->ftot) (void)hipFree(L->ftot);
-    delete L;
-}
-
 void loads_destroy(hakai_ctx* c) {
     if (!c || !c->loads) return;
     (void)hipSetDevice(c->device);
-    loads_free(c->loads);
+    delete c->loads;
     c->loads = nullptr;
-    c->d_ftot = nullptr;  // (owned by the state above)
+    c->d_ftot = nullptr;  // (a view of the state above)
 }
 
-// The state to add a part to: the context's, or a new one with its d_ftot (null: err is set).
-static Loads* loads_state(hakai_ctx* c, hipError_t* err) {
-    *err = hipSuccess;
-    if (c->loads) return c->loads;
-    Loads* L = new Loads();
-    std::memset(&L->a, 0, sizeof L->a);
-    *err = hipMalloc(&L->ftot, 3 * (size_t)c->nN * sizeof(double));
-    if (*err != hipSuccess) {
-        delete L;
-        return nullptr;
-    }
-    c->loads = L;
-    c->d_ftot = (double*)L->ftot;
-    return L;
+// The state to add a part to: the context's, or a new one with its d_ftot.
+static int loads_state(hakai_ctx* c) {
+    if (c->loads) return 0;
+    std::unique_ptr<Loads> L(new Loads());
+    HIPCHK(L->ftot.alloc(3 * (size_t)c->nN));
+    c->loads = L.release();
+    c->d_ftot = c->loads->ftot;
+    return 0;
 }
 
 // with_loads / with_walls: the parts of the sum to form (a step: both; the probes: one each)
 static int loads_launch(hakai_ctx* c, double t, double d_time, const double* fc, const double* t_rd, hipStream_t s,
                         bool with_loads, bool with_walls) {
-    Loads* L = c->loads;
-    LoadArgs a = L->a;
+    const Loads* L = c->loads;
+    LoadArgs a;
+    std::memset(&a, 0, sizeof a);
+    const Loads::LoadBufs& b = L->lb;
+    a.amp_n = b.amp_n, a.amp_off = b.amp_off, a.amp_t = b.amp_t, a.amp_v = b.amp_v;
+    a.cl_ptr = b.cl_ptr, a.cl_comp = b.cl_comp, a.cl_amp = b.cl_amp, a.cl_val = b.cl_val;
+    a.g_acc = b.g_acc, a.g_amp = b.g_amp, a.n_grav = L->n_grav;
+    a.pr_ptr = b.pr_ptr, a.pr_ent = b.pr_ent, a.pr_elem = b.pr_elem, a.pr_code = b.pr_code, a.pr_amp = b.pr_amp,
+    a.pr_val = b.pr_val;
+    const Loads::WallBufs& w = L->wb;
+    a.w_amp_n = w.amp_n, a.w_amp_off = w.amp_off, a.w_amp_t = w.amp_t, a.w_amp_v = w.amp_v;
+    a.w_tab = w.tab, a.w_amp = w.amp, a.w_mask = w.mask, a.n_wall = L->n_wall;
     a.fc = fc;
     a.mass = c->d_mass;
     a.coord = c->d_coord;
@@ -353,8 +353,9 @@ int hakai_clear_loads(hakai_ctx* c) {
     if (L->wl == 0) {
         hkc::loads_destroy(c);
     } else {  // the walls stay in force
-        free_all(L->owned_l);
+        L->lb = hkc::Loads::LoadBufs();
         L->cl = L->gr = L->pr = false;
+        L->n_grav = 0;
     }
     return hkc::history_restart(c);  // W_ext changes its meaning
 }
@@ -373,41 +374,30 @@ int hakai_set_loads(hakai_ctx* c, const hakai_loads_t* in) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIPCHK(hipStreamSynchronize(s));
-    std::vector<void*> owned;
-    LoadArgs a;
-    std::memset(&a, 0, sizeof a);
-    hipError_t e = upload(owned, &a.amp_n, P.amp_n, s);
-    if (e == hipSuccess) e = upload(owned, &a.amp_off, P.amp_off, s);
-    if (e == hipSuccess) e = upload(owned, &a.amp_t, P.amp_t, s);
-    if (e == hipSuccess) e = upload(owned, &a.amp_v, P.amp_v, s);
-    if (e == hipSuccess) e = upload(owned, &a.cl_ptr, P.cl_ptr, s);
-    if (e == hipSuccess) e = upload(owned, &a.cl_comp, P.cl_comp, s);
-    if (e == hipSuccess) e = upload(owned, &a.cl_amp, P.cl_amp, s);
-    if (e == hipSuccess) e = upload(owned, &a.cl_val, P.cl_val, s);
-    if (e == hipSuccess) e = upload(owned, &a.g_acc, P.g_acc, s);
-    if (e == hipSuccess) e = upload(owned, &a.g_amp, P.g_amp, s);
-    if (e == hipSuccess) e = upload(owned, &a.pr_ptr, P.pr_ptr, s);
-    if (e == hipSuccess) e = upload(owned, &a.pr_ent, P.pr_ent, s);
-    if (e == hipSuccess) e = upload(owned, &a.pr_elem, P.pr_elem, s);
-    if (e == hipSuccess) e = upload(owned, &a.pr_code, P.pr_code, s);
-    if (e == hipSuccess) e = upload(owned, &a.pr_amp, P.pr_amp, s);
-    if (e == hipSuccess) e = upload(owned, &a.pr_val, P.pr_val, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the plan's vectors go out of scope
-    hkc::Loads* L = e == hipSuccess ? hkc::loads_state(c, &e) : nullptr;
-    if (!L) {
-        free_all(owned);
-        return hip_fail(e, "set_loads: device copy of the plan");
-    }
-    free_all(L->owned_l);
-    L->owned_l.swap(owned);
-    LoadArgs& d = L->a;
-    d.amp_n = a.amp_n, d.amp_off = a.amp_off, d.amp_t = a.amp_t, d.amp_v = a.amp_v;
-    d.cl_ptr = a.cl_ptr, d.cl_comp = a.cl_comp, d.cl_amp = a.cl_amp, d.cl_val = a.cl_val;
-    d.g_acc = a.g_acc, d.g_amp = a.g_amp, d.n_grav = (int)P.g_amp.size();
-    d.pr_ptr = a.pr_ptr, d.pr_ent = a.pr_ent, d.pr_elem = a.pr_elem, d.pr_code = a.pr_code, d.pr_amp = a.pr_amp,
-    d.pr_val = a.pr_val;
+    hkc::Loads::LoadBufs b;
+    HIPCHK(upload(b.amp_n, P.amp_n, s));
+    HIPCHK(upload(b.amp_off, P.amp_off, s));
+    HIPCHK(upload(b.amp_t, P.amp_t, s));
+    HIPCHK(upload(b.amp_v, P.amp_v, s));
+    HIPCHK(upload(b.cl_ptr, P.cl_ptr, s));
+    HIPCHK(upload(b.cl_comp, P.cl_comp, s));
+    HIPCHK(upload(b.cl_amp, P.cl_amp, s));
+    HIPCHK(upload(b.cl_val, P.cl_val, s));
+    HIPCHK(upload(b.g_acc, P.g_acc, s));
+    HIPCHK(upload(b.g_amp, P.g_amp, s));
+    HIPCHK(upload(b.pr_ptr, P.pr_ptr, s));
+    HIPCHK(upload(b.pr_ent, P.pr_ent, s));
+    HIPCHK(upload(b.pr_elem, P.pr_elem, s));
+    HIPCHK(upload(b.pr_code, P.pr_code, s));
+    HIPCHK(upload(b.pr_amp, P.pr_amp, s));
+    HIPCHK(upload(b.pr_val, P.pr_val, s));
+    HIPCHK(hipStreamSynchronize(s));  // the plan's vectors go out of scope
+    if (int r = hkc::loads_state(c)) return r;
+    hkc::Loads* L = c->loads;
+    L->lb = std::move(b);  // (the previous plan's arrays are freed here)
+    L->n_grav = (int)P.g_amp.size();
     L->cl = !P.cl_ptr.empty();
-    L->gr = d.n_grav > 0;
+    L->gr = L->n_grav > 0;
     L->pr = !P.pr_ptr.empty();
     return hkc::history_restart(c);  // W_ext changes its meaning
 }
@@ -427,9 +417,9 @@ int hakai_clear_walls(hakai_ctx* c) {
     if (!L->has_loads()) {
         hkc::loads_destroy(c);
     } else {  // the loads stay in force
-        free_all(L->owned_w);
+        L->wb = hkc::Loads::WallBufs();
         L->wl = 0;
-        L->a.n_wall = 0;
+        L->n_wall = 0;
     }
     return hkc::history_restart(c);  // W_ext changes its meaning
 }
@@ -445,28 +435,19 @@ int hakai_set_walls(hakai_ctx* c, const hakai_walls_t* in) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIPCHK(hipStreamSynchronize(s));
-    std::vector<void*> owned;
-    LoadArgs a;
-    std::memset(&a, 0, sizeof a);
-    hipError_t e = upload(owned, &a.w_amp_n, P.amp_n, s);
-    if (e == hipSuccess) e = upload(owned, &a.w_amp_off, P.amp_off, s);
-    if (e == hipSuccess) e = upload(owned, &a.w_amp_t, P.amp_t, s);
-    if (e == hipSuccess) e = upload(owned, &a.w_amp_v, P.amp_v, s);
-    if (e == hipSuccess) e = upload(owned, &a.w_tab, P.tab, s);
-    if (e == hipSuccess) e = upload(owned, &a.w_amp, P.amp, s);
-    if (e == hipSuccess) e = upload(owned, &a.w_mask, P.mask, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the plan's vectors go out of scope
-    hkc::Loads* L = e == hipSuccess ? hkc::loads_state(c, &e) : nullptr;
-    if (!L) {
-        free_all(owned);
-        return hip_fail(e, "set_walls: device copy of the plan");
-    }
-    free_all(L->owned_w);
-    L->owned_w.swap(owned);
-    LoadArgs& d = L->a;
-    d.w_amp_n = a.w_amp_n, d.w_amp_off = a.w_amp_off, d.w_amp_t = a.w_amp_t, d.w_amp_v = a.w_amp_v;
-    d.w_tab = a.w_tab, d.w_amp = a.w_amp, d.w_mask = a.w_mask;
-    d.n_wall = P.n_wall;
+    hkc::Loads::WallBufs b;
+    HIPCHK(upload(b.amp_n, P.amp_n, s));
+    HIPCHK(upload(b.amp_off, P.amp_off, s));
+    HIPCHK(upload(b.amp_t, P.amp_t, s));
+    HIPCHK(upload(b.amp_v, P.amp_v, s));
+    HIPCHK(upload(b.tab, P.tab, s));
+    HIPCHK(upload(b.amp, P.amp, s));
+    HIPCHK(upload(b.mask, P.mask, s));
+    HIPCHK(hipStreamSynchronize(s));  // the plan's vectors go out of scope
+    if (int r = hkc::loads_state(c)) return r;
+    hkc::Loads* L = c->loads;
+    L->wb = std::move(b);  // (the previous plan's arrays are freed here)
+    L->n_wall = P.n_wall;
     L->wl = P.mask.empty() ? 1 : 2;
     return hkc::history_restart(c);  // W_ext changes its meaning
 }

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <memory>
 
 #include "../../include/hakai_hip.h"
 #include "hakai_device.hpp"
@@ -36,8 +37,6 @@
 #include "hakai_stable_dt.hpp"
 #include "hakai_stable_dt_dev.hpp"
 
-using hkc::dalloc;
-using hkc::dfree;
 using hkc::fail;
 using hkc::hip_fail;
 
@@ -222,20 +221,16 @@ namespace hkc {
 // Allocated at the context's first call, freed with the context, by a new model or by
 // hakai_clear_mass_scale.
 struct MassScale {
-    double* d_added = nullptr;  // [nE] mass added to each of the element's 8 nodes
-    double* d_mass0 = nullptr;  // [nN] the uploaded nodal mass
-    Part* d_part = nullptr;
-    Result* d_res = nullptr;
+    DevBuf<double> d_added;     // [nE] mass added to each of the element's 8 nodes
+    DevBuf<double> d_mass0;     // [nN] the uploaded nodal mass
+    DevBuf<Part> d_part;
+    DevBuf<Result> d_res;
     long long n_scaled = 0;     // elements with added > 0 after the last call
 };
 
 void mass_scale_destroy(hakai_ctx* c) {
     if (!c || !c->msc) return;
     (void)hipSetDevice(c->device);
-    dfree(c->msc->d_added);
-    dfree(c->msc->d_mass0);
-    dfree(c->msc->d_part);
-    dfree(c->msc->d_res);
     delete c->msc;
     c->msc = nullptr;
 }
@@ -272,17 +267,14 @@ extern "C" int hakai_mass_scale(hakai_ctx* c, double mass_scaling, double dt_tar
         hipStream_t st = c->stream;
         if (int rc = hkc::stable_dt_prepare(c, mass_scaling)) return rc;
         if (!c->msc) {
-            hkc::MassScale* s = new hkc::MassScale();
-            c->msc = s;
-            if (dalloc(&s->d_added, (size_t)nE) != hipSuccess || dalloc(&s->d_mass0, (size_t)nN) != hipSuccess ||
-                dalloc(&s->d_part, (size_t)nb) != hipSuccess || dalloc(&s->d_res, 1) != hipSuccess ||
-                hipMemsetAsync(s->d_added, 0, (size_t)nE * sizeof(double), st) != hipSuccess ||
-                hipMemcpyAsync(s->d_mass0, c->d_mass, (size_t)nN * sizeof(double), hipMemcpyDeviceToDevice, st) !=
-                    hipSuccess) {
-                (void)hipStreamSynchronize(st);
-                hkc::mass_scale_destroy(c);
-                return fail(HAKAI_ERR_DEVICE, "mass_scale: allocating the scratch failed");
-            }
+            std::unique_ptr<hkc::MassScale> s(new hkc::MassScale());
+            HIPCHK(s->d_added.alloc((size_t)nE));
+            HIPCHK(s->d_mass0.alloc((size_t)nN));
+            HIPCHK(s->d_part.alloc((size_t)nb));
+            HIPCHK(s->d_res.alloc(1));
+            HIPCHK(hipMemsetAsync(s->d_added, 0, (size_t)nE * sizeof(double), st));
+            HIPCHK(hipMemcpyAsync(s->d_mass0, c->d_mass, (size_t)nN * sizeof(double), hipMemcpyDeviceToDevice, st));
+            c->msc = s.release();
         }
         hkc::MassScale* s = c->msc;
         bool have_v0 = false;

@@ -33,6 +33,7 @@
 
 #include <climits>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "../../include/hakai_hip.h"
@@ -44,8 +45,6 @@
 #include "hakai_stable_dt_dev.hpp"
 #include "hakai_stable_dt_elem.hpp"
 
-using hkc::dalloc;
-using hkc::dfree;
 using hkc::fail;
 using hkc::hip_fail;
 
@@ -194,25 +193,18 @@ namespace hkc {
 // the result, the material table (filled per call: it depends on mass_scaling) and, once a caller
 // asks for them, the per-element arrays.
 struct StableDt {
-    Part* d_part = nullptr;
-    Result* d_res = nullptr;
-    hk::StableMat* d_mats = nullptr;
-    double* d_v0 = nullptr;             // [nE] V0 of every element, valid once a call has completed
+    DevBuf<Part> d_part;
+    DevBuf<Result> d_res;
+    DevBuf<hk::StableMat> d_mats;
+    DevBuf<double> d_v0;                // [nE] V0 of every element, valid once a call has completed
     bool have_v0 = false;
-    double* d_est = nullptr;
-    double* d_safe = nullptr;
+    DevBuf<double> d_est, d_safe;
     std::vector<hk::StableMat> h_mats;  // the table of the call in flight (the copy reads it)
 };
 
 void stable_dt_destroy(hakai_ctx* c) {
     if (!c || !c->sdt) return;
     (void)hipSetDevice(c->device);
-    dfree(c->sdt->d_part);
-    dfree(c->sdt->d_res);
-    dfree(c->sdt->d_mats);
-    dfree(c->sdt->d_v0);
-    dfree(c->sdt->d_est);
-    dfree(c->sdt->d_safe);
     delete c->sdt;
     c->sdt = nullptr;
 }
@@ -222,13 +214,12 @@ void stable_dt_destroy(hakai_ctx* c) {
 int stable_dt_prepare(hakai_ctx* c, double mass_scaling) {
     const long long nE = c->nE, nb = (nE + kEPB - 1) / kEPB;
     if (!c->sdt) {
-        StableDt* s = new StableDt();
-        c->sdt = s;
-        if (dalloc(&s->d_part, (size_t)nb) != hipSuccess || dalloc(&s->d_res, 1) != hipSuccess ||
-            dalloc(&s->d_mats, (size_t)c->nmat) != hipSuccess || dalloc(&s->d_v0, (size_t)nE) != hipSuccess) {
-            stable_dt_destroy(c);
-            return fail(HAKAI_ERR_DEVICE, "stable_dt: hipMalloc of the scratch failed");
-        }
+        std::unique_ptr<StableDt> s(new StableDt());
+        HIPCHK(s->d_part.alloc((size_t)nb));
+        HIPCHK(s->d_res.alloc(1));
+        HIPCHK(s->d_mats.alloc((size_t)c->nmat));
+        HIPCHK(s->d_v0.alloc((size_t)nE));
+        c->sdt = s.release();
     }
     StableDt* s = c->sdt;
     s->h_mats.resize((size_t)c->nmat);
@@ -265,8 +256,8 @@ extern "C" int hakai_stable_dt(hakai_ctx* c, double mass_scaling, double d_time,
     if (nE > 0) {
         if (int rc = hkc::stable_dt_prepare(c, mass_scaling)) return rc;
         hkc::StableDt* s = c->sdt;
-        if (dt_est_elem && !s->d_est) HIPCHK(dalloc(&s->d_est, (size_t)nE));
-        if (dt_safe_elem && !s->d_safe) HIPCHK(dalloc(&s->d_safe, (size_t)nE));
+        if (dt_est_elem && !s->d_est) HIPCHK(s->d_est.alloc((size_t)nE));
+        if (dt_safe_elem && !s->d_safe) HIPCHK(s->d_safe.alloc((size_t)nE));
         hipStream_t st = c->stream;
         Args a;
         a.coord = c->d_coord;

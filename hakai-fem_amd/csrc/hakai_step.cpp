@@ -65,10 +65,10 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
     // one GPU, small mesh: the nodal kernel applies the BCs (multi-GPU redoes interface nodes
     // after the nodal kernel, so the BCs must come after that)
     // (fuse_bc 2: at any size; large meshes measured slower with the fe gather, see kFuseBcMaxNodes)
-    const bool fuse_bc = c->nbc > 0 && c->d_bc_of_node && c->fuse_bc && !c->comm &&
+    const bool fuse_bc = c->bc.n > 0 && c->bc.d_of_node && c->fuse_bc && !c->comm &&
                          (c->nN <= kFuseBcMaxNodes || c->fuse_bc == 2);
     if (fuse_bc) {
-        na.bc_of_node = c->d_bc_of_node;
+        na.bc_of_node = c->bc.d_of_node;
         na.bc = ba;
     }
     int rc = 0;
@@ -96,7 +96,7 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
     rc = hkc::comm_post_nodal(c, d_time, &fix);
     if (rc) return rc;
     // boundary conditions (:585-617)
-    if (c->nbc > 0 && !fuse_bc) {
+    if (c->bc.n > 0 && !fuse_bc) {
         hkc::prof_begin(c, HAKAI_K_BC, &ep);
         HIPCHK(hk::launch_bc(ba, s));
         hkc::prof_end(c, &ep);
@@ -143,7 +143,7 @@ static int step_graph(hakai_ctx* c, double t, double d_time, int len) {
     const int p0 = c->sv.cur;
     const int gi = len == 2 ? 1 : 0;
     hipGraphExec_t& ge = c->gr.exec[gi][p0];
-    if (!c->d_tstep) HIPCHK(hkc::dalloc(&c->d_tstep, 2));
+    if (!c->d_tstep) HIPCHK(c->d_tstep.alloc(2));
     if (c->tdev_next != (long long)t) HIPCHK(hk::launch_set_step(c->d_tstep + (1 - p0), t - 1.0, s));
     if (ge && (c->gr.epoch[gi][p0] != c->epoch || c->gr.dt[gi][p0] != d_time || c->gr.len[gi][p0] != len)) {
         HIPCHK(hipStreamSynchronize(s));

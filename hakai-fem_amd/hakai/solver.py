@@ -233,7 +233,8 @@ class Solver:
 
     def stat(self, key: str) -> int:
         """Step-loop counter (hakai_stat): graph_steps, own_steps, own_rows, own_entries, own_superbatch, own_slots,
-        conn_patterns (0: the element kernel reads the plain connectivity array), conn_bytes."""
+        conn_patterns (0: the element kernel reads the plain connectivity array), conn_bytes, device_buffers (device
+        arrays the library holds now, over every context of the process)."""
         n = I64(0)
         check(self.L.hakai_stat(self.ctx, key.encode(), ctypes.byref(n)))
         return n.value

@@ -127,7 +127,9 @@ int hakai_graph_steps(hakai_ctx* ctx, int64_t* n_steps);
  * "own_round2" (summing passes that take a second entry per thread), "conn_patterns" (offset patterns
  * of the connectivity templates the element kernel reads; 0: it reads the plain connectivity array),
  * "conn_bytes" (connectivity bytes the element kernel reads per launch in that form),
- * "exchange_retries" (steps run again after a multi-GPU contact exchange block overflowed). */
+ * "exchange_retries" (steps run again after a multi-GPU contact exchange block overflowed),
+ * "device_buffers" (device arrays the library holds now, over every context of the process: equal
+ * before a context's creation and after its destruction). */
 int hakai_stat(hakai_ctx* ctx, const char* key, int64_t* value);
 int hakai_sync(hakai_ctx* ctx);
 /* Deletions so far (v2/HAKAI_j.jl:733-736): count, and up to cap (step, element 1-based) pairs. */
