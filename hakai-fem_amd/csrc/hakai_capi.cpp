@@ -28,6 +28,7 @@
 
 #include "../../include/hakai_hip.h"
 #include "hakai_conn_plan.hpp"
+#include "hakai_elem_history.hpp"
 #include "hakai_history.hpp"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
@@ -397,6 +398,7 @@ int hakai_destroy(hakai_ctx* c) {
     prof_harvest(c);
     hkc::graph_free(c);
     hkc::history_destroy(c);
+    hkc::elem_history_destroy(c);
     hkc::stable_dt_destroy(c);
     hkc::mass_scale_destroy(c);
     hkc::comm_destroy(c);
@@ -430,6 +432,7 @@ int hakai_upload_model(hakai_ctx* c, int64_t nNode, const double* coordmat, int6
     HIPCHK(hipSetDevice(c->device));
     (void)hipStreamSynchronize(c->stream);
     hkc::history_destroy(c);  // its buffers are sized for the previous mesh: enable again
+    hkc::elem_history_destroy(c);  // so are the element-set history's: enable again
     hkc::stable_dt_destroy(c);  // so is the stable-step scratch: the next call allocates it
     hkc::mass_scale_destroy(c);  // a new model starts unscaled (d_mass is uploaded again below)
     hkc::free_model(c);
@@ -649,6 +652,7 @@ int hakai_reset_state(hakai_ctx* c, int64_t n_ic, const int64_t* ic_dofs, const 
     c->state_ok = true;
     if (int r = hkc::contact_state_reset(c, c->h_velo0.data())) return r;
     if (int r = hkc::history_restart(c)) return r;
+    if (int r = hkc::elem_history_restart(c)) return r;
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
@@ -733,6 +737,7 @@ int hakai_upload_state(hakai_ctx* c, const hakai_state_t* st) {
     hkc::comm_reset(c);
     c->state_ok = true;
     if (int r = hkc::history_restart(c)) return r;
+    if (int r = hkc::elem_history_restart(c)) return r;
     if (c->contact) {
         if (int r = hkc::contact_state_reset(c, c->h_velo0.empty() ? nullptr : c->h_velo0.data())) return r;
         HIPCHK(hipStreamSynchronize(s));
@@ -913,6 +918,11 @@ int hakai_set_tuning(hakai_ctx* c, const char* key, int64_t value) {
     if (!std::strcmp(key, "history_one_block")) {  // the history reduction in one launch / two
         if (value < -1 || value > 1) return fail(HAKAI_ERR_ARG, "history_one_block must be -1 (by size), 0 or 1");
         c->hist_one_block = (int)value;
+        return 0;
+    }
+    if (!std::strcmp(key, "elem_history_one_block")) {  // the element-set history's reduction in one launch / two
+        if (value < -1 || value > 1) return fail(HAKAI_ERR_ARG, "elem_history_one_block must be -1 (by size), 0 or 1");
+        c->ehist_one_block = (int)value;
         return 0;
     }
     if (!std::strncmp(key, "contact_", 8)) {

@@ -16,6 +16,7 @@ namespace hkc {
 struct Comm;     // multi-GPU state (hakai_comm.cpp)
 struct Contact;  // contact search state (hakai_contact_state.hpp)
 struct History;  // history output state (hakai_history.hip)
+struct ElemHistory;  // element-set history state (hakai_elem_history.hip)
 struct StableDt; // stable-time-step scratch (hakai_stable_dt.hip)
 struct Loads;    // external loads and rigid walls (hakai_loads.hip)
 struct MassScale; // selective mass scaling (hakai_mass_scale.hip)
@@ -140,6 +141,9 @@ struct hakai_ctx {
     // history output (hakai_history_enable; hakai_history.hpp has the hooks)
     hkc::History* hist = nullptr;
     int hist_one_block = -1;           // tuning "history_one_block": -1 by size, 0 two launches, 1 one
+    // element-set history (hakai_elem_history_enable / _probe; hakai_elem_history.hpp has the hooks)
+    hkc::ElemHistory* ehist = nullptr;
+    int ehist_one_block = -1;          // tuning "elem_history_one_block": -1 by size, 0 two launches, 1 one
     // stable-time-step diagnostic (hakai_stable_dt; hakai_stable_dt.hpp): its scratch, null until the
     // first call, and the Poisson ratios its material table needs next to h_young
     hkc::StableDt* sdt = nullptr;

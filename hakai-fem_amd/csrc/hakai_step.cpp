@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/hakai_hip.h"
+#include "hakai_elem_history.hpp"
 #include "hakai_history.hpp"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
@@ -103,6 +104,8 @@ static int step_once(hakai_ctx* c, double t, double d_time, bool last, int phase
     }
     // history output: this step's sums, from the Q the nodal update consumed (still intact)
     if (c->hist && (rc = hkc::history_step(c, na, fix, t, c->gr.trd, s))) return rc;
+    // element-set history: the record of state k = t - 1 (d_u[cur] and the Gauss-point state are still its)
+    if (c->ehist && (rc = hkc::elem_history_step(c, t, c->gr.trd, s))) return rc;
     // element update (:662-667) + triaxiality (:677) + ductile deletion (:684-764), on the new
     // displacements: disp <- disp_new, disp_pre <- disp (:626-627)
     hk::ElemArgs ea = hkc::elem_args(c, 1 - par);

@@ -36,6 +36,14 @@ HISTORY_MAX_SETS = 15
 # the 16 values of a history record per set (hakai_history_enable), vectors as 3 components
 HISTORY_FIELDS = (("F_int", 0, 3), ("F_ext", 3, 3), ("P", 6, 3), ("KE", 9, 1), ("W_int", 10, 1), ("W_ext", 11, 1),
                   ("W_bc", 12, 1), ("U", 13, 3))
+ELEM_HISTORY_MAX_SETS = 15
+# the 24 values of an element-set history record per set (hakai_elem_history_enable), tensors as 6 components
+ELEM_HISTORY_FIELDS = (("N_active", 0, 1), ("N_deleted", 1, 1), ("V", 2, 1), ("V0", 3, 1), ("S", 4, 6), ("E", 10, 6),
+                       ("EQ", 16, 1), ("SE", 17, 1), ("PD", 18, 1), ("eqps_max", 19, 1), ("eqps_max_elem", 20, 1),
+                       ("mises_max", 21, 1), ("mises_max_elem", 22, 1), ("J_min", 23, 1))
+ELEM_HISTORY_CSV = ("N_active", "N_deleted", "V", "V0", "S_xx", "S_yy", "S_zz", "S_xy", "S_yz", "S_zx", "E_xx", "E_yy",
+                    "E_zz", "E_xy", "E_yz", "E_zx", "EQ", "SE", "PD", "eqps_max", "eqps_max_elem", "mises_max",
+                    "mises_max_elem", "J_min")
 
 
 class MaterialT(ctypes.Structure):
@@ -173,6 +181,14 @@ def lib() -> ctypes.CDLL:
         "hakai_history_write_csv": (c_int, [c_char_p, c_int32, POINTER(c_char_p), c_int64, PI64, PD, c_double]),
         "hakai_history_combine": (c_int, [c_int32, c_int32, c_int64, PI64, PD, PD, PI64, PD, PD]),
         "hakai_inp_history_sets": (c_int, [POINTER(InpModelT), PI32, PI64, PI64, c_int64, c_char_p, c_int64, PI32]),
+        "hakai_elem_history_enable": (c_int, [c_void_p, c_int32, PI64, PI64, c_int64, c_int64]),
+        "hakai_elem_history_disable": (c_int, [c_void_p]),
+        "hakai_elem_history_count": (c_int, [c_void_p, PI64, PI64]),
+        "hakai_elem_history_read": (c_int, [c_void_p, c_int64, c_int64, PI64, PD]),
+        "hakai_elem_history_probe": (c_int, [c_void_p, c_int32, PI64, PI64, PD, PD]),
+        "hakai_elem_history_write_csv": (c_int, [c_char_p, c_int32, POINTER(c_char_p), c_int64, PI64, PD, c_double]),
+        "hakai_elem_history_combine": (c_int, [c_int32, c_int32, c_int64, PI64, PD, PI64, PD]),
+        "hakai_inp_elem_history_sets": (c_int, [POINTER(InpModelT), PI32, PI64, PI64, c_int64, c_char_p, c_int64, PI32]),
         "hakai_stable_dt": (c_int, [c_void_p, c_double, c_double, POINTER(StableDtT), PD, PD]),
         "hakai_stable_dt_combine": (c_int, [c_int32, POINTER(StableDtT), POINTER(StableDtT)]),
         "hakai_stable_dt_write_csv": (c_int, [c_char_p, c_int64, PI64, POINTER(StableDtT), c_double]),
@@ -215,6 +231,9 @@ def exported_symbols() -> list[str]:
         "hakai_history_enable", "hakai_history_disable", "hakai_history_count", "hakai_history_read",
         "hakai_history_write_csv", "hakai_history_combine", "hakai_inp_history_sets",
         "hakai_stable_dt", "hakai_stable_dt_combine", "hakai_stable_dt_write_csv",
+        "hakai_elem_history_enable", "hakai_elem_history_disable", "hakai_elem_history_count",
+        "hakai_elem_history_read", "hakai_elem_history_probe", "hakai_elem_history_write_csv",
+        "hakai_elem_history_combine", "hakai_inp_elem_history_sets",
         "hakai_mass_scale", "hakai_mass_scale_get", "hakai_clear_mass_scale",
         "hakai_set_loads", "hakai_clear_loads", "hakai_load_force",
         "hakai_set_walls", "hakai_clear_walls", "hakai_wall_force",

@@ -188,6 +188,9 @@ class Model:
     # read_inp: the drivers' history sets of the deck (hakai_inp_history_sets) -- (names with "all"
     # first, [global 1-based node ids per kept set], names left out); None for a model built in code
     history_sets: tuple | None = None
+    # read_inp: the drivers' element-set history sets (hakai_inp_elem_history_sets) -- (names with "all"
+    # first, [global 1-based element ids per kept set], names left out); None for a model built in code
+    elem_history_sets: tuple | None = None
     # external loads (*Cload, *Dload, *Dsload of a deck; Solver applies them); None = no loads
     loads: Loads | None = None
     # rigid walls (*Rigid Wall of a deck; Solver applies them); None = no wall
@@ -364,6 +367,20 @@ def read_inp(path: str) -> Model:
                                        len(hnodes), text, cap, ctypes.byref(nd)))
         hnames = text.value.decode().split("\n")[:-1]
         hsets = [hnodes[hoff[s]:hoff[s + 1]].copy() for s in range(ns.value)]
+        # the sets HAKAI_ELEM_HISTORY records
+        es, ed = ctypes.c_int32(0), ctypes.c_int32(0)
+        eoff = np.zeros(_abi.ELEM_HISTORY_MAX_SETS + 1, np.int64)
+        check(L.hakai_inp_elem_history_sets(out, ctypes.byref(es), ptr(eoff, ctypes.c_int64), None, 0, None, 0,
+                                            ctypes.byref(ed)))
+        eelems = np.zeros(max(int(eoff[es.value]), 1), np.int64)
+        check(L.hakai_inp_elem_history_sets(out, ctypes.byref(es), ptr(eoff, ctypes.c_int64), ptr(eelems, ctypes.c_int64),
+                                            len(eelems), None, 0, ctypes.byref(ed)))
+        ecap = 1 << 16
+        etext = ctypes.create_string_buffer(ecap)
+        check(L.hakai_inp_elem_history_sets(out, ctypes.byref(es), ptr(eoff, ctypes.c_int64), None, 0, etext, ecap,
+                                            ctypes.byref(ed)))
+        enames = etext.value.decode().split("\n")[:-1]
+        esets = [eelems[eoff[s]:eoff[s + 1]].copy() for s in range(es.value)]
         ld, loads = m.loads, None
         if ld.n_cload or ld.n_grav or ld.n_press:
             lo = _arr(ld.amp_off, ld.n_amp, np.int64)
@@ -398,7 +415,8 @@ def read_inp(path: str) -> Model:
                        max_factor=float(m.vms_max_factor), repeat=bool(m.vms_repeat))
         return Model(coord, elem, emat, mats, bc, ic_d, ic_v, m.d_time, m.end_time, m.mass_scaling,
                      m.contact_flag, einst, name=str(path), contact_pairs=cps,
-                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]), loads=loads, walls=walls,
+                     history_sets=(hnames[:ns.value + 1], hsets, hnames[ns.value + 1:]),
+                     elem_history_sets=(enames[:es.value + 1], esets, enames[es.value + 1:]), loads=loads, walls=walls,
                      variable_mass_scaling=vms)
     finally:
         L.hakai_inp_free(out)

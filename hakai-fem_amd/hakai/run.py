@@ -229,6 +229,10 @@ def _setup_rank(glob, gdiag, rank, world, device, comm):
 def hakai_multi(fname: str, out_dir: str = "temp", local_ranks: int = 0, device: int = 0, verbose: bool = True):
     """HAKAI(fname) over torch.distributed's world (one process per GPU, already initialised with the
     nccl backend), or over `local_ranks` contexts of one process on `device`."""
+    if os.environ.get("HAKAI_ELEM_HISTORY"):
+        raise ValueError("HAKAI_ELEM_HISTORY is set: the N-GPU driver does not write elem_history.csv yet (the ranks' "
+                         "records exist, Solver.elem_history / elem_history_group) -- run the deck on one GPU "
+                         "(hakai.hakai / the hakai CLI) or unset the variable")
     glob = read_inp(fname)
     if glob.loads is not None and not glob.loads.empty:
         raise ValueError(f"{fname}: the deck has external loads (*Cload / *Dload / *Dsload); the N-GPU driver does "

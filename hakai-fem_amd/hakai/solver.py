@@ -286,6 +286,61 @@ class Solver:
         check(self.L.hakai_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values), ptr(ke)))
         return _history_dict(steps, values, ke)
 
+    # -- element-set history ------------------------------------------------------------------------
+    @staticmethod
+    def _elem_sets(sets):
+        sets = [np.ascontiguousarray(s, np.int64).ravel() for s in sets]
+        off = np.zeros(len(sets) + 1, np.int64)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        elems = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), np.int64)
+        return len(sets), off, elems
+
+    def elem_history_enable(self, sets=(), stride: int = 1, capacity: int = 1 << 16):
+        """Element-set records (hakai_elem_history_enable): `sets` is a list of 1-based element id
+        arrays (at most 15; set 0, every element, is always there). The record of state k is kept
+        when k % stride == 0, the newest `capacity` of them. On a rank the ids are the rank's local
+        ones and the records its partials (elem_history_group combines them)."""
+        n, off, elems = self._elem_sets(sets)
+        check(self.L.hakai_elem_history_enable(self.ctx, n, ptr(off, I64), ptr(elems, I64), int(stride),
+                                               int(capacity)))
+        self._elem_history_sets = n + 1
+
+    def elem_history_disable(self):
+        check(self.L.hakai_elem_history_disable(self.ctx))
+
+    def elem_history_count(self) -> tuple[int, int]:
+        """(records written since the last (re)start, how many of the newest are still held)."""
+        nw, nh = I64(0), I64(0)
+        check(self.L.hakai_elem_history_count(self.ctx, ctypes.byref(nw), ctypes.byref(nh)))
+        return nw.value, nh.value
+
+    def elem_history(self, first: int | None = None, n: int | None = None) -> dict:
+        """The held records (or records [first, first+n) counted from the (re)start): ``steps`` (n,),
+        ``values`` (n, sets, 24) and one array per field of ``_abi.ELEM_HISTORY_FIELDS`` --
+        (n, sets, 6) for S and E, (n, sets) for the rest."""
+        nw, nh = self.elem_history_count()
+        if first is None:
+            first = nw - nh
+        if n is None:
+            n = nw - first
+        steps = np.zeros(max(n, 0), np.int64)
+        values = np.zeros((max(n, 0), self._elem_history_sets, 24))
+        check(self.L.hakai_elem_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values)))
+        return _elem_history_dict(steps, values)
+
+    def elem_history_probe(self, sets=(), per_elem: bool = False) -> dict:
+        """The record of the current state (hakai_elem_history_probe), with sets of its own: a dict by
+        field name, (sets, 6) for S and E, (sets,) for the rest, ``values`` (sets, 24); with per_elem
+        also ``per_elem`` (nElement, 20): V, V0, S[6], E[6], EQ, SE, PD, eqps_max, q_max, V / V0."""
+        n, off, elems = self._elem_sets(sets)
+        values = np.zeros((n + 1, 24))
+        pe = np.zeros((self.model.nElement, 20)) if per_elem else None
+        check(self.L.hakai_elem_history_probe(self.ctx, n, ptr(off, I64), ptr(elems, I64), ptr(values), ptr(pe)))
+        out = {k: v[0] for k, v in _elem_history_dict(np.zeros(1, np.int64), values[None]).items() if k != "steps"}
+        if per_elem:
+            out["per_elem"] = pe
+        return out
+
     # -- stable time step -------------------------------------------------------------------------
     def stable_dt(self, d_time: float | None = None, mass_scaling: float | None = None,
                   per_element: bool = False) -> dict:
@@ -408,6 +463,35 @@ def history_group(solvers: list[Solver], first: int | None = None, n: int | None
     return history_combine([sv.history(first, n) for sv in solvers])
 
 
+def _elem_history_dict(steps, values) -> dict:
+    from ._abi import ELEM_HISTORY_FIELDS
+    out = dict(steps=steps, values=values)
+    for name, lo, w in ELEM_HISTORY_FIELDS:
+        out[name] = values[:, :, lo:lo + w] if w > 1 else values[:, :, lo]
+    return out
+
+
+def elem_history_combine(parts: list[dict]) -> dict:
+    """The ranks' partial records (Solver.elem_history() dicts, in rank order) as the record of the
+    whole model (hakai_elem_history_combine): sums added in rank order, extremes with the lower id
+    among equals. The same dict as Solver.elem_history()."""
+    shapes = {(p["steps"].shape, p["values"].shape) for p in parts}
+    if len(shapes) != 1:
+        raise ValueError(f"elem_history_combine: the ranks hold different record counts or sets: {sorted(shapes)}")
+    steps = np.ascontiguousarray(np.stack([p["steps"] for p in parts]), np.int64)
+    values = np.ascontiguousarray(np.stack([p["values"] for p in parts]), np.float64)
+    R, n, S = values.shape[0], values.shape[1], values.shape[2]
+    so, vo = np.zeros(n, np.int64), np.zeros((n, S, 24))
+    check(lib().hakai_elem_history_combine(R, S, n, ptr(steps, I64), ptr(values), ptr(so, I64), ptr(vo)))
+    return _elem_history_dict(so, vo)
+
+
+def elem_history_group(solvers: list[Solver], first: int | None = None, n: int | None = None) -> dict:
+    """The record of the whole model from a group of ranks (solvers[r] = rank r): every rank's
+    elem_history(first, n), combined in rank order."""
+    return elem_history_combine([sv.elem_history(first, n) for sv in solvers])
+
+
 STABLE_DT_KEYS = tuple(name for name, _ in StableDtT._fields_)
 
 
@@ -525,6 +609,28 @@ def read_history_csv(path: str) -> dict:
     steps = np.array([int(r[0]) for r in rows], np.int64)
     time = np.array([float(r[1]) for r in rows])
     values = np.array([[float(x) for x in r[2:]] for r in rows]).reshape(len(rows), len(sets), 16)
+    return dict(sets=sets, steps=steps, time=time, values=values)
+
+
+def write_elem_history_csv(path: str, set_names, steps, values, d_time: float):
+    """Element-set records as CSV (hakai_elem_history_write_csv): values (n, sets, 24), set 0's name first."""
+    steps = np.ascontiguousarray(steps, np.int64)
+    values = np.ascontiguousarray(values, np.float64)
+    names = (ctypes.c_char_p * len(set_names))(*[str(s).encode() for s in set_names])
+    assert values.shape == (len(steps), len(set_names), 24), values.shape
+    check(lib().hakai_elem_history_write_csv(str(path).encode(), len(set_names), names, len(steps), ptr(steps, I64),
+                                             ptr(values), float(d_time)))
+
+
+def read_elem_history_csv(path: str) -> dict:
+    """An elem_history.csv back as dict(sets, steps, time, values (n, sets, 24)): the same doubles."""
+    with open(path) as fh:
+        head = fh.readline().strip().split(",")
+        rows = [ln.strip().split(",") for ln in fh if ln.strip()]
+    sets = [h[:-len("_N_active")] for h in head[2::24]]
+    steps = np.array([int(r[0]) for r in rows], np.int64)
+    time = np.array([float(r[1]) for r in rows])
+    values = np.array([[float(x) for x in r[2:]] for r in rows]).reshape(len(rows), len(sets), 24)
     return dict(sets=sets, steps=steps, time=time, values=values)
 
 

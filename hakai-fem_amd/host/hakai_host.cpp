@@ -134,6 +134,8 @@ struct Elset {
     std::string name, instance_name, part_name;
     int instance_id = 0, part_id = 0;
     std::vector<long long> elements;
+    std::vector<long long> plain;  // a list without "internal" (the reference's reader skips it): for the
+                                   // element-set history only
 };
 struct Amp {
     std::string name;
@@ -177,6 +179,10 @@ struct Owned {
     std::vector<int32_t> wl_amp_n, wl_amp;
     std::vector<int64_t> wl_amp_off, wl_node_off, wl_nodes;
     std::vector<double> wl_amp_t, wl_amp_v, wl_origin, wl_normal, wl_motion, wl_stiff, wl_scale, wl_damp, wl_fric;
+    // the deck's *Elset ... instance= sets in deck order, "<instance>.<elset>", global 1-based element
+    // ids ascending (hakai_inp_elem_history_sets; not part of hakai_inp_model_t)
+    std::vector<std::string> es_names;
+    std::vector<int64_t> es_off{0}, es_elems;
 };
 
 void read_lines(const char* path, std::vector<std::string>& lines) {
@@ -340,10 +346,16 @@ void parse(const char* path, Owned& o) {
                 if (has(line(r), "*")) break;
                 for (auto& tok : split(nospace(line(r)), ',', false)) es.elements.push_back(parse_i(tok));
             }
+        } else if (ss.size() == 3) {
+            for (long long r = i + 1; r <= n; ++r) {
+                if (has(line(r), "*")) break;
+                for (auto& tok : split(nospace(line(r)), ',', false)) es.plain.push_back(parse_i(tok));
+            }
         }
         ELSET.push_back(es);
     }
-    (void)ELSET;  // surfaces / contact pairs: consumed by the contact path
+    // (consumed by surfaces / contact pairs, *Dload and, kept in the model's private storage below, by
+    // the element-set history)
 
     // ---- global model (:567-621)
     long long nNode = 0, nElement = 0;
@@ -885,6 +897,19 @@ void parse(const char* path, Owned& o) {
                 o.ic_dofs.push_back(d);
                 o.ic_val.push_back(c.value[j]);
             }
+    for (auto& E : ELSET) {
+        if (E.instance_id <= 0) continue;
+        std::vector<int64_t> es;
+        for (long long el : E.elements.empty() ? E.plain : E.elements)
+            es.push_back(el + INST[E.instance_id - 1].element_offset);
+        std::sort(es.begin(), es.end());
+        es.erase(std::unique(es.begin(), es.end()), es.end());
+        for (int64_t el : es)
+            if (el < 1 || el > nElement) throw ParseError{"*Elset " + E.name + ": element out of range"};
+        o.es_names.push_back(E.instance_name + "." + E.name);
+        o.es_elems.insert(o.es_elems.end(), es.begin(), es.end());
+        o.es_off.push_back((int64_t)o.es_elems.size());
+    }
     for (auto& I : INST) {
         o.inst_noff.push_back(I.node_offset);
         o.inst_eoff.push_back(I.element_offset);
@@ -1008,9 +1033,66 @@ void pusai_table(double P[8][3][8]) {  // cal_Pusai_hexa, v2/HAKAI_j.jl:1895-194
         }
 }
 
+// HAKAI_ELEM_HISTORY=<stride>: the sets of the drivers' element-set history -- "all" (set 0), one per
+// instance, one per material when there are several, then the deck's *Elset ... instance= sets,
+// HAKAI_ELEM_HISTORY_MAX_SETS in all.
+void elem_history_driver_sets(const hakai_inp_model_t* M, std::vector<std::string>& names, std::vector<int64_t>& off,
+                              std::vector<int64_t>& elems, std::vector<std::string>& dropped) {
+    const Owned* o = reinterpret_cast<const Owned*>(M);  // pub is the first member
+    names.assign(1, "all");
+    off.assign(1, 0);
+    elems.clear();
+    dropped.clear();
+    auto add = [&](const std::string& name, const std::vector<int64_t>& es) {
+        if ((int)names.size() > HAKAI_ELEM_HISTORY_MAX_SETS) {
+            dropped.push_back(name);
+            return;
+        }
+        names.push_back(name);
+        elems.insert(elems.end(), es.begin(), es.end());
+        off.push_back((int64_t)elems.size());
+    };
+    for (int i = 0; i < M->n_instance; ++i) {
+        std::vector<int64_t> es;
+        for (int64_t e = 0; e < M->instance_nElement[i]; ++e) es.push_back(M->instance_element_offset[i] + e + 1);
+        add("inst" + std::to_string(i + 1), es);
+    }
+    for (int j = 1; M->nMat > 1 && j <= M->nMat; ++j) {
+        std::vector<int64_t> es;
+        for (int64_t e = 0; e < M->nElement; ++e)
+            if (M->element_material[e] == j) es.push_back(e + 1);
+        add("mat" + std::to_string(j), es);
+    }
+    for (size_t s = 0; s < o->es_names.size(); ++s)
+        add(o->es_names[s], std::vector<int64_t>(o->es_elems.begin() + o->es_off[s], o->es_elems.begin() + o->es_off[s + 1]));
+}
+
 }  // namespace
 
 extern "C" {
+
+int hakai_inp_elem_history_sets(const hakai_inp_model_t* model, int32_t* n_sets, int64_t* set_off, int64_t* set_elems,
+                                int64_t elems_cap, char* names, int64_t names_cap, int32_t* n_dropped) {
+    if (!model || !n_sets || !set_off) return fail(HAKAI_ERR_ARG, "inp_elem_history_sets: null");
+    std::vector<std::string> nm, dropped;
+    std::vector<int64_t> off, elems;
+    elem_history_driver_sets(model, nm, off, elems, dropped);
+    std::string text;
+    for (const std::string& s : nm) text += s + "\n";
+    for (const std::string& s : dropped) text += s + "\n";
+    if (set_elems && elems_cap < (int64_t)elems.size())
+        return fail(HAKAI_ERR_ARG, "inp_elem_history_sets: %lld elements, room for %lld", (long long)elems.size(),
+                    (long long)elems_cap);
+    if (names && names_cap < (int64_t)text.size() + 1)
+        return fail(HAKAI_ERR_ARG, "inp_elem_history_sets: %lld bytes of names, room for %lld",
+                    (long long)text.size() + 1, (long long)names_cap);
+    *n_sets = (int32_t)nm.size() - 1;
+    if (n_dropped) *n_dropped = (int32_t)dropped.size();
+    std::copy(off.begin(), off.end(), set_off);
+    if (set_elems) std::copy(elems.begin(), elems.end(), set_elems);
+    if (names) std::memcpy(names, text.c_str(), text.size() + 1);
+    return 0;
+}
 
 int hakai_inp_read(const char* path, hakai_inp_model_t** out) {
     if (!path || !out) return fail(HAKAI_ERR_ARG, "null");
@@ -1138,6 +1220,27 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
                                       n_steps / hist_stride + 1)))  // the ring holds the whole run
             return r;
     }
+    // HAKAI_ELEM_HISTORY=<stride>: the element-set history of set 0, the instances, the materials and the
+    // deck's element sets, a record every <stride> states plus the final state's, written to
+    // out_dir/elem_history.csv at the end
+    long long ehist_stride = 0;
+    std::vector<std::string> ehist_names;
+    std::vector<int64_t> ehist_off, ehist_elems;
+    if (const char* hv = std::getenv("HAKAI_ELEM_HISTORY")) {
+        ehist_stride = std::atoll(hv);
+        if (ehist_stride < 1) return fail(HAKAI_ERR_ARG, "HAKAI_ELEM_HISTORY=%s: the stride must be >= 1", hv);
+    }
+    if (ehist_stride > 0) {
+        std::vector<std::string> dropped;
+        elem_history_driver_sets(M, ehist_names, ehist_off, ehist_elems, dropped);
+        if (verbose)
+            for (const std::string& d : dropped)
+                std::fprintf(stderr, "elem_history: set %s left out (at most %d sets)\n", d.c_str(),
+                             HAKAI_ELEM_HISTORY_MAX_SETS);
+        if ((r = hakai_elem_history_enable(c, (int32_t)ehist_names.size() - 1, ehist_off.data(), ehist_elems.data(),
+                                           ehist_stride, n_steps / ehist_stride + 1)))  // the ring holds the whole run
+            return r;
+    }
     // VTK files are formatted and written by the writer's thread team while the device steps on;
     // the arrays go straight from the device into the writer's fill buffers (zero-copy commit).
     const char* se = std::getenv("HAKAI_VTK_SYNC");  // 1: wait for every file (A/B measurements)
@@ -1262,6 +1365,24 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
         const std::string path = std::string(out_dir) + "/history.csv";
         if ((r = hakai_history_write_csv(path.c_str(), (int32_t)names.size(), names.data(), nh, steps.data(),
                                          values.data(), d_time)))
+            return r;
+    }
+    if (ehist_stride > 0) {  // the in-step records, then the probe's record of the last state
+        int64_t nw = 0, nh = 0;
+        if ((r = hakai_elem_history_count(c, &nw, &nh))) return r;
+        const size_t W = ehist_names.size() * HAKAI_ELEM_HISTORY_FIELDS;
+        std::vector<int64_t> steps((size_t)nh + 1);
+        std::vector<double> values(((size_t)nh + 1) * W);
+        if ((r = hakai_elem_history_read(c, nw - nh, nh, steps.data(), values.data()))) return r;
+        steps[(size_t)nh] = n_steps;
+        if ((r = hakai_elem_history_probe(c, (int32_t)ehist_names.size() - 1, ehist_off.data(), ehist_elems.data(),
+                                          values.data() + (size_t)nh * W, nullptr)))
+            return r;
+        std::vector<const char*> names;
+        for (const std::string& nm : ehist_names) names.push_back(nm.c_str());
+        const std::string path = std::string(out_dir) + "/elem_history.csv";
+        if ((r = hakai_elem_history_write_csv(path.c_str(), (int32_t)names.size(), names.data(), nh + 1, steps.data(),
+                                              values.data(), d_time)))
             return r;
     }
     if (dt_check) {

@@ -212,6 +212,8 @@ int hakai_profile_read(hakai_ctx* ctx, int kernel, double* total_ms, int64_t* la
  *   "graph"             steps per captured hipGraph (even, default 16; 0 = stream mode);
  *   "history_one_block" history output's reduction: -1 (default) one launch up to 2048 nodes, two
  *                       above; 0: two launches; 1: one (the same bits either way);
+ *   "elem_history_one_block" the element-set history's reduction: -1 (default) one launch up to 256
+ *                       elements, two above; 0: two launches; 1: one (the same bits either way);
  *   "contact_event_cap", "contact_candidate_cap", "contact_full_rebuild": contact buffers and
  *                       rebuild policy;
  *   "contact_exchange_deletions", "contact_exchange_bins", "contact_exchange_events": multi-GPU
@@ -304,6 +306,90 @@ int hakai_history_write_csv(const char* path, int32_t n_names, const char* const
  * refused call leaves the outputs untouched. */
 int hakai_history_combine(int32_t n_ranks, int32_t n_total, int64_t n, const int64_t* steps, const double* values,
                           const double* ke_seed, int64_t* steps_out, double* values_out, double* ke_seed_out);
+
+/* ---- element-set history: volume, mean stress and strain, energy split per element set -------- */
+/* The element side of a history: functions of the Gauss-point state and the current geometry,
+ * evaluated only at record steps by kernels of their own (nothing a step computes changes: the
+ * trajectory is the same bits with the feature on and off). Set 0 is every element, sets 1..n_sets
+ * the caller's; an element may be in several. An element counts as active if element_flag == 1;
+ * every sum and extreme runs over the active elements of the set. With x = coord + u_k,
+ * a_k = |det(P_k x^T)| at Gauss point k (the cal_Pusai_hexa table; hakai_stable_dt's determinant),
+ * a0_k the same on coord, and sigma, eps (xx, yy, zz, xy, yz, zx), eqps the stored state:
+ *    0     N_active      as a double
+ *    1     N_deleted     elements of the set whose deletion step is non-zero
+ *    2     V             sum a_k
+ *    3     V0            sum a0_k
+ *    4-9   S[c]          sum a_k sigma_k[c] (the mean stress is S / V, formed by the reader)
+ *   10-15  E[c]          sum a_k eps_k[c]
+ *   16     EQ            sum a_k eqps_k
+ *   17     SE            sum a_k w_e(sigma_k), w_e = q^2 / (6 G) + p^2 / (2 K), p = tr sigma / 3, q the
+ *                        Mises stress, K = (Dn + 2 Do) / 3: the recoverable strain energy
+ *   18     PD            sum a0_k w_p(eqps_k), w_p the area under the material's piecewise linear
+ *                        hardening curve (yield0 at the first row, the last slope continued beyond
+ *                        the last row, 0 for an elastic material): the plastic dissipation.
+ *                        Reference weights, because plastic flow is isochoric
+ *   19,20  eqps_max      the largest eqps_k and the global 1-based id of its element (the lowest id
+ *                        among equals); both 0 for a set without active elements
+ *   21,22  mises_max     the largest q_k and its element, the same rule
+ *   23     J_min         min over elements of V_e / V0_e; +inf for a set without active elements
+ * SE + PD is not W_int of hakai_history: the radial return takes H from the segment at the start
+ * of the increment, the stress update carries no rotation, the volume changes, and a deleted
+ * element's energy leaves the sums (eroded energy is not tracked). DESIGN.md "Element-set history"
+ * has the measured gap.
+ * With the history enabled, step t = k+1 writes -- after its nodal update and BCs, before its
+ * element update, when k % stride == 0 -- the record (k, values) of state k into a ring of the
+ * newest `capacity` records. Records describe states 0 .. N-1 of an N-step run; the probe gives the
+ * state after the last step. hakai_reset_state and hakai_upload_state return the count to 0;
+ * hakai_upload_model disables the feature; hakai_set_bc, loads, walls and mass scaling leave it
+ * alone (there are no accumulators). A step a contact overflow poisoned leaves no record. Enable and
+ * disable drop captured step graphs. It is independent of hakai_history: either, both or neither.
+ * The sums are taken in a fixed tree over the element numbers (8 elements of a wave, 4 waves of a
+ * 32-element chunk, then chunks pairwise in order): the same bits for every tuning setting and for
+ * both launch forms, tuning "elem_history_one_block" (-1 default: one workgroup in one launch up to
+ * 256 elements, else chunk partials and a combining launch; 0; 1). Counts, extremes and ids are
+ * exact.
+ * On N ranks every element belongs to one rank: a rank's record is its partial over its local
+ * elements (set ids are the rank's local 1-based ids, the recorded ids global: element offset +
+ * local id), nothing is exchanged, no interface is needed, and hakai_elem_history_combine forms the
+ * record of the whole model. Its counts, extremes and ids equal the one-GPU record's; its sums are
+ * within the same rounding bound but not the same bits (the tree runs over local numbers). */
+#define HAKAI_ELEM_HISTORY_MAX_SETS 15
+#define HAKAI_ELEM_HISTORY_FIELDS 24
+/* set_off[n_sets+1] into set_elems (1-based element ids; an empty set is allowed and records zeros,
+ * 0 and +inf). HAKAI_ERR_ARG, and nothing changes: an id out of range, a duplicate within a set,
+ * more than 15 sets, stride < 1, capacity < 1. HAKAI_ERR_STATE without a model. */
+int hakai_elem_history_enable(hakai_ctx* ctx, int32_t n_sets, const int64_t* set_off, const int64_t* set_elems,
+                              int64_t stride, int64_t capacity);
+int hakai_elem_history_disable(hakai_ctx* ctx);
+/* records written since the last (re)start, and how many of the newest the ring still holds */
+int hakai_elem_history_count(hakai_ctx* ctx, int64_t* n_written, int64_t* n_held);
+/* syncs; records [first, first+n) counted from the (re)start, must still be held (else
+ * HAKAI_ERR_ARG); steps[n], values[n][(n_sets+1)][24] (either pointer may be NULL) */
+int hakai_elem_history_read(hakai_ctx* ctx, int64_t first, int64_t n, int64_t* steps, double* values);
+/* The record of the CURRENT state, off the step loop (like hakai_stable_dt: it needs a state, runs
+ * on the context's stream, synchronises, writes only its own scratch and leaves captured graphs
+ * valid; the steps before and after it are the same bits with and without it), with sets of its own:
+ * values[(n_sets+1)][24]. per_elem (optional): [nElement][20] = V, V0, S[6], E[6], EQ, SE, PD,
+ * eqps_max, q_max, V / V0 of every active element, zeros for the others. It works whether or not
+ * the in-step history is enabled. HAKAI_ERR_ARG as for enable. */
+int hakai_elem_history_probe(hakai_ctx* ctx, int32_t n_sets, const int64_t* set_off, const int64_t* set_elems,
+                             double* values, double* per_elem);
+/* Host helper (no GPU): n records as CSV -- one header line step,time,<set>_<field>,... (fields
+ * N_active, N_deleted, V, V0, S_xx, S_yy, S_zz, S_xy, S_yz, S_zx, E_xx .. E_zx, EQ, SE, PD, eqps_max,
+ * eqps_max_elem, mises_max, mises_max_elem, J_min; set_names[n_names] with set 0 first), one line
+ * per record with time = step * d_time and every value as %.17g (parses back to the same double). */
+int hakai_elem_history_write_csv(const char* path, int32_t n_names, const char* const* set_names, int64_t n,
+                                 const int64_t* steps, const double* values, double d_time);
+/* Host helper (no GPU): the ranks' partial records into the record of the whole model. Inputs in
+ * rank order: steps[n_ranks][n], values[n_ranks][n][n_total][24], n_total = n_sets + 1. Fields 0-18
+ * are added in rank order, ((p_0 + p_1) + p_2) + ..., one rounding per addition; 19-22 take the
+ * larger value and the lower id among equals (a rank without active elements in the set holds 0, 0
+ * and never wins against one with); 23 takes the smaller value. One rank is the identity.
+ * HAKAI_ERR_ARG: a null array (may be NULL only when n == 0), n_ranks < 1, n_total outside 1..16,
+ * n < 0. HAKAI_ERR_STATE: the ranks' step numbers differ. A refused call leaves the outputs
+ * untouched. */
+int hakai_elem_history_combine(int32_t n_ranks, int32_t n_total, int64_t n, const int64_t* steps,
+                               const double* values, int64_t* steps_out, double* values_out);
 
 /* ---- stable time step: per-element estimate and lower bound, reduced on the device ----------- */
 /* The reference takes its step from the deck (v2/HAKAI_j.jl:112-116) and never checks it against the
@@ -743,6 +829,13 @@ void hakai_vtk_writer_destroy(hakai_vtk_writer* w);
  * out_dir/stable_dt.csv (hakai_stable_dt_write_csv) at the end; verbose: one stderr line the first
  * time d_time > dt_est and one the first time d_time > dt_safe, each naming the element. The VTK
  * files and stdout are the same bytes with and without; unset, nothing changes.
+ * Env HAKAI_ELEM_HISTORY=<stride> (>= 1, else HAKAI_ERR_ARG) enables the element-set history for the
+ * run and writes out_dir/elem_history.csv (hakai_elem_history_write_csv) at the end: the in-step
+ * records of the whole run plus one final hakai_elem_history_probe record for the last state. Sets:
+ * "all", then "inst<i>" per instance, then "mat<j>" per material when nMat > 1, then the deck's
+ * *Elset ... instance= sets as "<instance>.<elset>" in deck order, 15 at most (verbose: the ones left
+ * out are named on stderr). Unset, every byte of output is as before. The N-GPU driver (hakai.run)
+ * refuses to run with the variable set.
  * The deck's loads (hakai_inp_model_t::loads) are applied with hakai_set_loads, its rigid walls
  * (hakai_inp_model_t::walls) with hakai_set_walls. */
 int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbose);
@@ -753,6 +846,13 @@ int hakai_run_inp(const char* fname, const char* out_dir, int device, int verbos
  * HAKAI_ERR_ARG if nodes_cap or names_cap is too small. */
 int hakai_inp_history_sets(const hakai_inp_model_t* model, int32_t* n_sets, int64_t* set_off, int64_t* set_nodes,
                            int64_t nodes_cap, char* names, int64_t names_cap, int32_t* n_dropped);
+/* The sets of the element-set history output (HAKAI_ELEM_HISTORY), the contract of
+ * hakai_inp_history_sets: n_sets (without set 0), set_off[n_sets+1] (room for 16) into set_elems (global
+ * 1-based element ids, ascending; NULL: only the offsets), names: "all", the n_sets kept names, then
+ * the n_dropped names left out, each ended by a newline (NULL: none). HAKAI_ERR_ARG if elems_cap or
+ * names_cap is too small. The deck's *Elset sets live in the model's private storage. */
+int hakai_inp_elem_history_sets(const hakai_inp_model_t* model, int32_t* n_sets, int64_t* set_off, int64_t* set_elems,
+                                int64_t elems_cap, char* names, int64_t names_cap, int32_t* n_dropped);
 
 #ifdef __cplusplus
 }

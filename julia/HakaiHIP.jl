@@ -234,6 +234,39 @@ function history_combine(parts::Vector{<:Tuple})
     return so, vo, ko
 end
 
+# Element-set history (hakai_elem_history_enable, include/hakai_hip.h): per element set the counts,
+# volumes, volume-weighted stress and strain sums, strain energy, plastic dissipation and extremes of
+# state k, kept when k % stride == 0 in a ring of the newest `capacity` records. sets: vectors of
+# 1-based element ids (at most 15); set 0, every element, is always there.
+const ELEM_HISTORY_FIELDS = (:N_active, :N_deleted, :V, :V0, :S_xx, :S_yy, :S_zz, :S_xy, :S_yz, :S_zx, :E_xx, :E_yy,
+                             :E_zz, :E_xy, :E_yz, :E_zx, :EQ, :SE, :PD, :eqps_max, :eqps_max_elem, :mises_max,
+                             :mises_max_elem, :J_min)
+function elem_history_enable(c::Ctx, sets::Vector{<:AbstractVector{<:Integer}}; stride::Integer = 1,
+                             capacity::Integer = 1 << 16)
+    off = Int64[0]; elems = Int64[]
+    for s in sets
+        append!(elems, s); push!(off, length(elems))
+    end
+    check(ccall((:hakai_elem_history_enable, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Int64, Int64),
+                c.p, length(sets), off, elems, stride, capacity))
+    return length(sets) + 1
+end
+elem_history_disable(c::Ctx) = check(ccall((:hakai_elem_history_disable, lib), Cint, (Ptr{Cvoid},), c.p))
+function elem_history_count(c::Ctx)
+    nw = Ref{Int64}(0); nh = Ref{Int64}(0)
+    check(ccall((:hakai_elem_history_count, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c.p, nw, nh))
+    return nw[], nh[]
+end
+# the held records of an element-set history with n_total sets (elem_history_enable's return value):
+# steps[n], values[24, n_total, n] (field, set, record; ELEM_HISTORY_FIELDS)
+function elem_history(c::Ctx, n_total::Integer)
+    nw, nh = elem_history_count(c)
+    steps = zeros(Int64, nh); values = zeros(Float64, 24, n_total, nh)
+    check(ccall((:hakai_elem_history_read, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                c.p, nw - nh, nh, steps, values))
+    return steps, values
+end
+
 # cal_node_stress_strain (v2/HAKAI_j.jl:3408-3486) on the device -> the fields of NodeDataType
 # (node_stress / node_strain nNode x 6 like the reference; node_plastic_strain stays zero, :450)
 function node_stress_strain(c::Ctx, nNode::Integer)
