@@ -20,11 +20,11 @@
 // (hakai_elem_history_gp.hpp has the reasons).
 // The launch boundary is the only hand-off between blocks: no atomics, no flags, no spins. Every sum
 // is a node of one binary tree over the element numbers (a wave's 8 elements, the block's 4 waves as
-// (w0+w1)+(w2+w3), then chunks and groups of chunks pairwise, neighbours first; a subtree without a
-// right sibling moves up unchanged), so its bits depend on the element numbering and the sets alone,
-// not on the launch form or the grid. Counts, extremes and ids are exact and order-free; `>` and `<`
-// let a NaN never win. On a rank the tree runs over the rank's local elements; nothing is exchanged,
-// hakai_elem_history_combine (host) combines the ranks' records.
+// (w0+w1)+(w2+w3), then chunks and groups of chunks by hakai_pair_tree.hpp), so its bits depend on the
+// element numbering and the sets alone, not on the launch form or the grid. Counts, extremes and ids
+// are exact and order-free; `>` and `<` let a NaN never win. On a rank the tree runs over the rank's
+// local elements; nothing is exchanged, hakai_elem_history_combine (host) combines the ranks' records.
+// The sets' masks and the record ring on the host are hakai_record_sets.hpp's and hakai_record_ring.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +38,8 @@
 #include "hakai_elem_history.hpp"
 #include "hakai_elem_history_gp.hpp"
 #include "hakai_internal.hpp"
+#include "hakai_pair_tree.hpp"
+#include "hakai_record_ring.hpp"
 
 using hkc::fail;
 using hkc::hip_fail;
@@ -103,24 +105,8 @@ __device__ __forceinline__ double eh_neutral(int f) {
     return f <= kELastSum ? 0.0 : (f == 19 || f == 21) ? -1.0 : HUGE_VAL;
 }
 
-// One binary tree over items pushed in order: an item whose index has k trailing one bits closes
-// k subtrees. `stk` is this thread's column of an LDS array [depth][kEB].
-struct EhPairTree {
-    double* stk;
-    int depth = 0;
-    unsigned idx = 0;
-    __device__ __forceinline__ void push(double x) {
-        for (unsigned m = idx; m & 1u; m >>= 1) x = stk[(--depth) * kEB] + x;
-        stk[(depth++) * kEB] = x;
-        ++idx;
-    }
-    __device__ __forceinline__ double fold() {  // the open subtrees, smallest first into its left neighbour
-        if (depth == 0) return 0.0;
-        double x = stk[(--depth) * kEB];
-        while (depth > 0) x = stk[(--depth) * kEB] + x;
-        return x;
-    }
-};
+// A thread's tree (hakai_pair_tree.hpp): `stk` is its column of an LDS array [depth][kEB].
+using EhTree = PairTree<kEB, unsigned>;
 
 // The largest of the 8 lanes' values and 0 (elem_hist_max8: order-free, a NaN never wins).
 __device__ __forceinline__ double eh_max8(double v) {
@@ -268,7 +254,7 @@ template <bool kAhead>
 __device__ __forceinline__ void eh_group(const EhArgs& a, long long g, double* lds_w, double* stk) {
     const int tid = threadIdx.x;
     const int W = a.S * kEF;
-    EhPairTree tree[kESlots];
+    EhTree tree[kESlots];
     double rv[kESlots], rid[kESlots];
 #pragma unroll
     for (int q = 0; q < kESlots; ++q) {
@@ -415,12 +401,11 @@ constexpr long long kElemHistOneBlockChunks = hk::kEGroup;
 struct ElemHistory {
     bool on = false;             // the in-step history is enabled (else only the probe's scratch lives)
     int n_sets = 0;
-    long long stride = 1, cap = 1;
     long long nchunks = 0, ngroups = 1;
     DevBuf<hk::ElemHistMat> d_mats;
     DevBuf<unsigned short> d_mask;
-    DevBuf<double> d_gp, d_ring;
-    DevBuf<unsigned long long> d_count;
+    DevBuf<double> d_gp;
+    RecordRing ring;
     // the probe's own scratch, sized at its calls
     int p_sets = -1;
     DevBuf<unsigned short> d_pmask;
@@ -436,7 +421,7 @@ void elem_history_destroy(hakai_ctx* c) {
 
 int elem_history_restart(hakai_ctx* c) {
     if (!c->ehist || !c->ehist->on) return 0;
-    HIPCHK(hipMemsetAsync(c->ehist->d_count, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c->ehist->ring.restart(c->stream));
     return 0;
 }
 
@@ -452,28 +437,6 @@ static int eh_state(hakai_ctx* c) {
     H->nchunks = (c->nE + hk::kEChunk - 1) / hk::kEChunk;
     H->ngroups = std::max<long long>(1, (H->nchunks + hk::kEGroup - 1) / hk::kEGroup);
     c->ehist = H.release();
-    return 0;
-}
-
-// The per-element set mask of the caller's sets; HAKAI_ERR_ARG names `what`.
-static int eh_mask(const hakai_ctx* c, const char* what, int32_t n_sets, const int64_t* set_off,
-                   const int64_t* set_elems, std::vector<unsigned short>& mask) {
-    if (n_sets < 0 || n_sets > HAKAI_ELEM_HISTORY_MAX_SETS)
-        return fail(HAKAI_ERR_ARG, "%s: %d sets (0..%d)", what, n_sets, HAKAI_ELEM_HISTORY_MAX_SETS);
-    if (n_sets > 0 && !set_off) return fail(HAKAI_ERR_ARG, "%s: null set_off", what);
-    mask.assign((size_t)c->nE, 0);
-    for (int s = 0; s < n_sets; ++s) {
-        if (set_off[s] < 0 || set_off[s + 1] < set_off[s] || (set_off[s + 1] > set_off[s] && !set_elems))
-            return fail(HAKAI_ERR_ARG, "%s: bad set_off of set %d", what, s + 1);
-        for (int64_t i = set_off[s]; i < set_off[s + 1]; ++i) {
-            const int64_t e = set_elems[i];
-            if (e < 1 || e > c->nE)
-                return fail(HAKAI_ERR_ARG, "%s: element %lld of set %d out of 1..%lld", what, (long long)e, s + 1, c->nE);
-            if ((mask[e - 1] >> s) & 1u)
-                return fail(HAKAI_ERR_ARG, "%s: element %lld twice in set %d", what, (long long)e, s + 1);
-            mask[e - 1] |= (unsigned short)(1u << s);
-        }
-    }
     return 0;
 }
 
@@ -507,15 +470,15 @@ static bool eh_one_block(const hakai_ctx* c) {
 int elem_history_step(hakai_ctx* c, double t, const double* t_rd, hipStream_t s) {
     const ElemHistory* H = c->ehist;
     if (!H || !H->on) return 0;
-    if (!t_rd && ((long long)t - 1) % H->stride != 0) return 0;  // stream mode: the host knows the step
+    if (!t_rd && ((long long)t - 1) % H->ring.stride != 0) return 0;  // stream mode: the host knows the step
     hk::EhArgs a = eh_args(c);
     a.mask = H->d_mask;
     a.S = H->n_sets + 1;
     a.gp = H->d_gp;
-    a.ring = H->d_ring;
-    a.count = H->d_count;
-    a.stride = H->stride;
-    a.cap = H->cap;
+    a.ring = H->ring.d_ring;
+    a.count = H->ring.d_count;
+    a.stride = H->ring.stride;
+    a.cap = H->ring.cap;
     a.t = t;
     a.t_rd = t_rd;
     HIPCHK(hk::launch_elem_history(a, eh_one_block(c), s));
@@ -531,34 +494,28 @@ int hakai_elem_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_o
     if (!c) return fail(HAKAI_ERR_ARG, "null");
     if (!c->model_ok) return fail(HAKAI_ERR_STATE, "elem_history_enable before upload_model");
     std::vector<unsigned short> mask;
-    if (int r = hkc::eh_mask(c, "elem_history_enable", n_sets, set_off, set_elems, mask)) return r;
-    if (stride < 1 || capacity < 1)
-        return fail(HAKAI_ERR_ARG, "elem_history_enable: stride %lld, capacity %lld (both >= 1)", (long long)stride,
-                    (long long)capacity);
+    if (int r = hkc::parse_sets("elem_history_enable", "element", HAKAI_ELEM_HISTORY_MAX_SETS, c->nE, n_sets, set_off,
+                                set_elems, mask))
+        return r;
     const size_t W = (size_t)hk::kEF * (size_t)(n_sets + 1);
-    if (capacity > ((int64_t)1 << 40) / (int64_t)(1 + W))
-        return fail(HAKAI_ERR_ARG, "elem_history_enable: capacity too large");
+    if (int r = hkc::ring_check("elem_history_enable", stride, capacity, (int64_t)W)) return r;
     HIPCHK(hipSetDevice(c->device));
     if (int r = hkc::eh_state(c)) return r;
     hkc::ElemHistory* H = c->ehist;
     hipStream_t st = c->stream;
     // the new buffers first: a failed allocation leaves the previous state in force
     hkc::DevBuf<unsigned short> d_mask;
-    hkc::DevBuf<double> d_gp, d_ring;
-    hkc::DevBuf<unsigned long long> d_count;
+    hkc::DevBuf<double> d_gp;
+    hkc::RecordRing ring;
     HIPCHK(d_mask.upload(mask, st));
     HIPCHK(d_gp.alloc_zero((size_t)H->ngroups * W, st));
-    HIPCHK(d_ring.alloc_zero((size_t)capacity * (1 + W), st));
-    HIPCHK(d_count.alloc_zero(1, st));
+    HIPCHK(ring.alloc(W, stride, capacity, st));
     HIPCHK(hipStreamSynchronize(st));  // (before mask goes; the stream's earlier steps are done with the old buffers)
     hkc::graph_invalidate(c);  // the captured steps change
     H->d_mask = std::move(d_mask);
     H->d_gp = std::move(d_gp);
-    H->d_ring = std::move(d_ring);
-    H->d_count = std::move(d_count);
+    H->ring = std::move(ring);
     H->n_sets = n_sets;
-    H->stride = stride;
-    H->cap = capacity;
     H->on = true;
     return 0;
 }
@@ -573,8 +530,7 @@ int hakai_elem_history_disable(hakai_ctx* c) {
         H->on = false;
         H->d_mask.free();
         H->d_gp.free();
-        H->d_ring.free();
-        H->d_count.free();
+        H->ring = hkc::RecordRing();
     }
     return 0;
 }
@@ -583,37 +539,14 @@ int hakai_elem_history_count(hakai_ctx* c, int64_t* n_written, int64_t* n_held) 
     if (!c) return fail(HAKAI_ERR_ARG, "null");
     if (!c->ehist || !c->ehist->on) return fail(HAKAI_ERR_STATE, "element history is not enabled");
     HIPCHK(hipSetDevice(c->device));
-    unsigned long long n = 0;
-    HIPCHK(hipMemcpyAsync(&n, c->ehist->d_count, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (n_written) *n_written = (int64_t)n;
-    if (n_held) *n_held = std::min<int64_t>((int64_t)n, c->ehist->cap);
-    return 0;
+    return c->ehist->ring.count(c->stream, n_written, n_held);
 }
 
 int hakai_elem_history_read(hakai_ctx* c, int64_t first, int64_t n, int64_t* steps, double* values) {
-    int64_t nw = 0, nh = 0;
-    if (int r = hakai_elem_history_count(c, &nw, &nh)) return r;
-    const hkc::ElemHistory* H = c->ehist;
-    if (first < 0 || n < 0 || first + n > nw || (n > 0 && first < nw - nh))
-        return fail(HAKAI_ERR_ARG, "elem_history_read: records [%lld, %lld) of %lld written, the newest %lld held",
-                    (long long)first, (long long)(first + n), (long long)nw, (long long)nh);
-    const size_t SW = (size_t)hk::kEF * (size_t)(H->n_sets + 1), W = 1 + SW;
-    if (n > 0 && (steps || values)) {  // at most two runs of consecutive ring slots
-        std::vector<double> buf((size_t)n * W);
-        const int64_t s0 = first % H->cap, n0 = std::min<int64_t>(n, H->cap - s0);
-        HIPCHK(hipMemcpyAsync(buf.data(), H->d_ring + (size_t)s0 * W, (size_t)n0 * W * sizeof(double),
-                              hipMemcpyDeviceToHost, c->stream));
-        if (n > n0)
-            HIPCHK(hipMemcpyAsync(buf.data() + (size_t)n0 * W, H->d_ring, (size_t)(n - n0) * W * sizeof(double),
-                                  hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (int64_t i = 0; i < n; ++i) {
-            if (steps) std::memcpy(&steps[i], &buf[(size_t)i * W], sizeof(int64_t));
-            if (values) std::memcpy(values + (size_t)i * SW, &buf[(size_t)i * W + 1], SW * sizeof(double));
-        }
-    }
-    return 0;
+    if (!c) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->ehist || !c->ehist->on) return fail(HAKAI_ERR_STATE, "element history is not enabled");
+    HIPCHK(hipSetDevice(c->device));
+    return c->ehist->ring.read(c->stream, "elem_history_read", first, n, steps, values);
 }
 
 int hakai_elem_history_probe(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, const int64_t* set_elems,
@@ -621,7 +554,9 @@ int hakai_elem_history_probe(hakai_ctx* c, int32_t n_sets, const int64_t* set_of
     if (!c || !values) return fail(HAKAI_ERR_ARG, "elem_history_probe: null");
     if (!c->state_ok) return fail(HAKAI_ERR_STATE, "elem_history_probe without state");
     std::vector<unsigned short> mask;
-    if (int r = hkc::eh_mask(c, "elem_history_probe", n_sets, set_off, set_elems, mask)) return r;
+    if (int r = hkc::parse_sets("elem_history_probe", "element", HAKAI_ELEM_HISTORY_MAX_SETS, c->nE, n_sets, set_off,
+                                set_elems, mask))
+        return r;
     HIPCHK(hipSetDevice(c->device));
     if (int r = hkc::eh_state(c)) return r;
     hkc::ElemHistory* H = c->ehist;

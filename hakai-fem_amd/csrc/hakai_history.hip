@@ -10,9 +10,9 @@
 //   k_history_one     both in one launch: one block walks every group (small decks)
 //
 // The launch boundary is the only hand-off between blocks: no atomics, no flags, no spins. Every
-// sum is a node of one binary tree over the node numbers (pairs of neighbours, then pairs of
-// pairs; a subtree without a right sibling moves up unchanged), so its bits depend on the node
-// numbering and the sets alone, not on the launch form or the grid.
+// sum is a node of the one binary tree over the node numbers (hakai_pair_tree.hpp), so its bits depend
+// on the node numbering and the sets alone, not on the launch form or the grid. The sets' mask and the
+// record ring on the host are hakai_record_sets.hpp's and hakai_record_ring.hpp's.
 // Compiled without contraction: Q is formed with k_nodal's additions in k_nodal's order.
 // On a rank (a context with a communicator) the same tree runs over the rank's local numbering and
 // over the nodes it owns: a node shared with the rank below counts nowhere, and at a node shared
@@ -29,6 +29,8 @@
 #include "hakai_history.hpp"
 #include "hakai_internal.hpp"
 #include "hakai_kernels.hpp"
+#include "hakai_pair_tree.hpp"
+#include "hakai_record_ring.hpp"
 
 using hkc::fail;
 using hkc::hip_fail;
@@ -73,26 +75,8 @@ struct HistArgs {
     double t;
 };
 
-// One binary tree over items pushed in order: an item whose index has k trailing one bits closes
-// k subtrees. `stk` is this thread's column of an LDS array [depth][kHB].
-struct PairTree {
-    double* stk;
-    int depth = 0;
-    unsigned long long idx = 0;
-    __device__ __forceinline__ void push(double x) {
-#pragma clang fp contract(off)
-        for (unsigned long long m = idx; m & 1ull; m >>= 1) x = stk[(--depth) * kHB] + x;
-        stk[(depth++) * kHB] = x;
-        ++idx;
-    }
-    __device__ __forceinline__ double fold() {  // the open subtrees, smallest first into its left neighbour
-#pragma clang fp contract(off)
-        if (depth == 0) return 0.0;
-        double x = stk[(--depth) * kHB];
-        while (depth > 0) x = stk[(--depth) * kHB] + x;
-        return x;
-    }
-};
+// A thread's tree (hakai_pair_tree.hpp): `stk` is its column of an LDS array [depth][kHB].
+using HistTree = PairTree<kHB, unsigned long long>;
 
 // Q_k of node n from the source launch_nodal selected: k_nodal's additions in k_nodal's order
 // (MODE as there: 0 padded table, 1 CSR, 2 uploaded Q, 3 owner-computed sums + rows).
@@ -249,7 +233,7 @@ __device__ __forceinline__ void hist_group(const HistArgs& h, long long g, doubl
 #pragma clang fp contract(off)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int S16 = h.S * kHF;
-    PairTree tree;
+    HistTree tree;
     tree.stk = stk + tid;
     const long long c0 = g * kHGroup, c1 = c0 + kHGroup < h.nchunks ? c0 + kHGroup : h.nchunks;
     for (long long ch = c0; ch < c1; ++ch) {
@@ -307,7 +291,7 @@ __device__ __forceinline__ void hist_finish(const HistArgs& h, double* stk, doub
     const unsigned long long cnt = *h.count;  // (thread 0 stores the new count after the last barrier)
     double x = 0.0;
     if (active) {
-        PairTree tree;
+        HistTree tree;
         tree.stk = stk + tid;
         const long long g0 = r * sub, g1 = g0 + sub < h.ngroups ? g0 + sub : h.ngroups;
         // (eight loads in flight: the pushes walk an LDS stack and would wait for each load in turn)
@@ -415,15 +399,13 @@ constexpr long long kHistOneBlockChunks = hk::kHGroup;
 
 struct History {
     int n_sets = 0;
-    long long stride = 1, cap = 1;
     long long nchunks = 0, ngroups = 0;
     bool need_seed = true;
     DevBuf<double> d_du_prev;
     DevBuf<unsigned short> d_set;
     DevBuf<unsigned char> d_presc;
-    DevBuf<double> d_acc, d_ke, d_ring;
-    DevBuf<unsigned long long> d_count;
-    DevBuf<double> d_gp;
+    DevBuf<double> d_acc, d_ke, d_gp;
+    RecordRing ring;
     int n_up = 0;                // a rank: its nodes shared with the rank above, ascending, and their
     DevBuf<int> d_up_node;       // positions in the exchange buffers (hist_q_up)
     DevBuf<int> d_up_slot;
@@ -443,7 +425,7 @@ int history_restart(hakai_ctx* c) {
     if (!H) return 0;
     H->need_seed = true;
     const int S = H->n_sets + 1;
-    HIPCHK(hipMemsetAsync(H->d_count, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(H->ring.restart(c->stream));
     HIPCHK(hipMemsetAsync(H->d_acc, 0, 3 * S * sizeof(double), c->stream));
     HIPCHK(hipMemsetAsync(H->d_ke, 0, S * sizeof(double), c->stream));
     return 0;
@@ -477,10 +459,10 @@ static hk::HistArgs hist_args(hakai_ctx* c, const hk::NodalArgs& na, const CommF
     h.ngroups = H->ngroups;
     h.acc = H->d_acc;
     h.ke_seed = H->d_ke;
-    h.ring = H->d_ring;
-    h.count = H->d_count;
-    h.stride = H->stride;
-    h.cap = H->cap;
+    h.ring = H->ring.d_ring;
+    h.count = H->ring.d_count;
+    h.stride = H->ring.stride;
+    h.cap = H->ring.cap;
     h.up_node = H->d_up_node;
     h.up_slot = H->d_up_slot;
     h.n_up = H->n_up;
@@ -528,28 +510,12 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
     if (c->comm && !hkc::comm_iface_set(c))  // a rank's node ownership comes from its interface
         return fail(HAKAI_ERR_STATE, "history_enable: a context with a communicator needs hakai_set_interface first "
                     "(an empty interface counts)");
-    if (n_sets < 0 || n_sets > HAKAI_HISTORY_MAX_SETS)
-        return fail(HAKAI_ERR_ARG, "history_enable: %d sets (0..%d)", n_sets, HAKAI_HISTORY_MAX_SETS);
-    if (n_sets > 0 && !set_off) return fail(HAKAI_ERR_ARG, "history_enable: null set_off");
-    if (stride < 1 || capacity < 1)
-        return fail(HAKAI_ERR_ARG, "history_enable: stride %lld, capacity %lld (both >= 1)", (long long)stride,
-                    (long long)capacity);
+    std::vector<unsigned short> set;
+    if (int r = hkc::parse_sets("history_enable", "node", HAKAI_HISTORY_MAX_SETS, c->nN, n_sets, set_off, set_nodes,
+                                set))
+        return r;
     const int S = n_sets + 1;
-    if (capacity > ((int64_t)1 << 40) / (1 + 16 * S)) return fail(HAKAI_ERR_ARG, "history_enable: capacity too large");
-    std::vector<unsigned short> set((size_t)c->nN, 0);
-    for (int s = 0; s < n_sets; ++s) {
-        if (set_off[s] < 0 || set_off[s + 1] < set_off[s] || (set_off[s + 1] > set_off[s] && !set_nodes))
-            return fail(HAKAI_ERR_ARG, "history_enable: bad set_off of set %d", s + 1);
-        for (int64_t i = set_off[s]; i < set_off[s + 1]; ++i) {
-            const int64_t n = set_nodes[i];
-            if (n < 1 || n > c->nN)
-                return fail(HAKAI_ERR_ARG, "history_enable: node %lld of set %d out of 1..%lld", (long long)n, s + 1,
-                            c->nN);
-            if ((set[n - 1] >> s) & 1u)
-                return fail(HAKAI_ERR_ARG, "history_enable: node %lld twice in set %d", (long long)n, s + 1);
-            set[n - 1] |= (unsigned short)(1u << s);
-        }
-    }
+    if (int r = hkc::ring_check("history_enable", stride, capacity, 16 * S)) return r;
     // a rank: the nodes shared with the rank below are that rank's (the contact search's owner rule);
     // the nodes shared with the rank above ascending, each with its position in the exchange buffers
     std::vector<int> up_node, up_slot;
@@ -570,8 +536,6 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
     std::unique_ptr<hkc::History> H(new hkc::History());
     H->n_up = (int)up_node.size();
     H->n_sets = n_sets;
-    H->stride = stride;
-    H->cap = capacity;
     H->nchunks = (c->nN + hk::kHB - 1) / hk::kHB;
     H->ngroups = (H->nchunks + hk::kHGroup - 1) / hk::kHGroup;
     const size_t nN = (size_t)c->nN, S16 = 16 * (size_t)S;
@@ -581,8 +545,7 @@ int hakai_history_enable(hakai_ctx* c, int32_t n_sets, const int64_t* set_off, c
     HIPCHK(H->d_presc.alloc_zero(nN, st));
     HIPCHK(H->d_acc.alloc_zero(3 * (size_t)S, st));
     HIPCHK(H->d_ke.alloc_zero((size_t)S, st));
-    HIPCHK(H->d_ring.alloc_zero((size_t)capacity * (1 + S16), st));
-    HIPCHK(H->d_count.alloc_zero(1, st));
+    HIPCHK(H->ring.alloc(S16, stride, capacity, st));
     HIPCHK(H->d_gp.alloc_zero((size_t)H->ngroups * S16, st));
     if (H->n_up > 0) {
         HIPCHK(H->d_up_node.alloc_zero(up_node.size(), st));
@@ -612,36 +575,15 @@ int hakai_history_count(hakai_ctx* c, int64_t* n_written, int64_t* n_held) {
     if (!c) return fail(HAKAI_ERR_ARG, "null");
     if (!c->hist) return fail(HAKAI_ERR_STATE, "history is not enabled");
     HIPCHK(hipSetDevice(c->device));
-    unsigned long long n = 0;
-    HIPCHK(hipMemcpyAsync(&n, c->hist->d_count, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (n_written) *n_written = (int64_t)n;
-    if (n_held) *n_held = std::min<int64_t>((int64_t)n, c->hist->cap);
-    return 0;
+    return c->hist->ring.count(c->stream, n_written, n_held);
 }
 
 int hakai_history_read(hakai_ctx* c, int64_t first, int64_t n, int64_t* steps, double* values, double* ke_seed) {
-    int64_t nw = 0, nh = 0;
-    if (int r = hakai_history_count(c, &nw, &nh)) return r;
+    if (!c) return fail(HAKAI_ERR_ARG, "null");
+    if (!c->hist) return fail(HAKAI_ERR_STATE, "history is not enabled");
+    HIPCHK(hipSetDevice(c->device));
     const hkc::History* H = c->hist;
-    if (first < 0 || n < 0 || first + n > nw || (n > 0 && first < nw - nh))
-        return fail(HAKAI_ERR_ARG, "history_read: records [%lld, %lld) of %lld written, the newest %lld held",
-                    (long long)first, (long long)(first + n), (long long)nw, (long long)nh);
-    const size_t S16 = 16 * (size_t)(H->n_sets + 1), W = 1 + S16;
-    if (n > 0 && (steps || values)) {  // at most two runs of consecutive ring slots
-        std::vector<double> buf((size_t)n * W);
-        const int64_t s0 = first % H->cap, n0 = std::min<int64_t>(n, H->cap - s0);
-        HIPCHK(hipMemcpyAsync(buf.data(), H->d_ring + (size_t)s0 * W, (size_t)n0 * W * sizeof(double),
-                              hipMemcpyDeviceToHost, c->stream));
-        if (n > n0)
-            HIPCHK(hipMemcpyAsync(buf.data() + (size_t)n0 * W, H->d_ring, (size_t)(n - n0) * W * sizeof(double),
-                                  hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (int64_t i = 0; i < n; ++i) {
-            if (steps) std::memcpy(&steps[i], &buf[(size_t)i * W], sizeof(int64_t));
-            if (values) std::memcpy(values + (size_t)i * S16, &buf[(size_t)i * W + 1], S16 * sizeof(double));
-        }
-    }
+    if (int r = H->ring.read(c->stream, "history_read", first, n, steps, values)) return r;
     if (ke_seed) {
         HIPCHK(hipMemcpyAsync(ke_seed, H->d_ke, (H->n_sets + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));

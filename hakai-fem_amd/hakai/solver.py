@@ -246,19 +246,37 @@ class Solver:
         return n.value
 
     # -- history output --------------------------------------------------------------------------
+    @staticmethod
+    def _record_sets(sets):
+        """(n, off, ids): a list of 1-based id arrays in the form the C entry points take."""
+        sets = [np.ascontiguousarray(s, np.int64).ravel() for s in sets]
+        off = np.zeros(len(sets) + 1, np.int64)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        ids = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), np.int64)
+        return len(sets), off, ids
+
+    def _records(self, count, read, shape, first, n, *more):
+        """The held records, or records [first, first+n) counted from the (re)start, through a
+        count-and-read pair: steps (n,), values (n, *shape). `more` are read's further arguments."""
+        nw, nh = count()
+        if first is None:
+            first = nw - nh
+        if n is None:
+            n = nw - first
+        steps = np.zeros(max(n, 0), np.int64)
+        values = np.zeros((max(n, 0), *shape))
+        check(read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values), *more))
+        return steps, values
+
     def history_enable(self, sets=(), stride: int = 1, capacity: int = 1 << 16):
         """Per-step sums over node sets (hakai_history_enable): `sets` is a list of 1-based node id
         arrays (at most 15; set 0, every node, is always there). A record is kept every `stride`
         states, the newest `capacity` of them. On a rank (after set_interface) the ids are the
         rank's local ones (dist.local_sets), stride and capacity the same on every rank, and the
         records are the rank's partial sums over the nodes it owns (history_group combines them)."""
-        sets = [np.ascontiguousarray(s, np.int64).ravel() for s in sets]
-        off = np.zeros(len(sets) + 1, np.int64)
-        off[1:] = np.cumsum([len(s) for s in sets])
-        nodes = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), np.int64)
-        check(self.L.hakai_history_enable(self.ctx, len(sets), ptr(off, I64), ptr(nodes, I64), int(stride),
-                                          int(capacity)))
-        self._history_sets = len(sets) + 1
+        n, off, nodes = self._record_sets(sets)
+        check(self.L.hakai_history_enable(self.ctx, n, ptr(off, I64), ptr(nodes, I64), int(stride), int(capacity)))
+        self._history_sets = n + 1
 
     def history_disable(self):
         check(self.L.hakai_history_disable(self.ctx))
@@ -274,33 +292,18 @@ class Solver:
         ``values`` (n, sets, 16), ``ke_seed`` (sets,) and one array per field of
         ``_abi.HISTORY_FIELDS`` -- (n, sets, 3) for F_int, F_ext, P, U; (n, sets) for KE, W_int,
         W_ext, W_bc."""
-        nw, nh = self.history_count()
-        if first is None:
-            first = nw - nh
-        if n is None:
-            n = nw - first
-        S = self._history_sets
-        steps = np.zeros(max(n, 0), np.int64)
-        values = np.zeros((max(n, 0), S, 16))
-        ke = np.zeros(S)
-        check(self.L.hakai_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values), ptr(ke)))
+        ke = np.zeros(self._history_sets)
+        steps, values = self._records(self.history_count, self.L.hakai_history_read, (self._history_sets, 16), first,
+                                      n, ptr(ke))
         return _history_dict(steps, values, ke)
 
     # -- element-set history ------------------------------------------------------------------------
-    @staticmethod
-    def _elem_sets(sets):
-        sets = [np.ascontiguousarray(s, np.int64).ravel() for s in sets]
-        off = np.zeros(len(sets) + 1, np.int64)
-        off[1:] = np.cumsum([len(s) for s in sets])
-        elems = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), np.int64)
-        return len(sets), off, elems
-
     def elem_history_enable(self, sets=(), stride: int = 1, capacity: int = 1 << 16):
         """Element-set records (hakai_elem_history_enable): `sets` is a list of 1-based element id
         arrays (at most 15; set 0, every element, is always there). The record of state k is kept
         when k % stride == 0, the newest `capacity` of them. On a rank the ids are the rank's local
         ones and the records its partials (elem_history_group combines them)."""
-        n, off, elems = self._elem_sets(sets)
+        n, off, elems = self._record_sets(sets)
         check(self.L.hakai_elem_history_enable(self.ctx, n, ptr(off, I64), ptr(elems, I64), int(stride),
                                                int(capacity)))
         self._elem_history_sets = n + 1
@@ -318,21 +321,14 @@ class Solver:
         """The held records (or records [first, first+n) counted from the (re)start): ``steps`` (n,),
         ``values`` (n, sets, 24) and one array per field of ``_abi.ELEM_HISTORY_FIELDS`` --
         (n, sets, 6) for S and E, (n, sets) for the rest."""
-        nw, nh = self.elem_history_count()
-        if first is None:
-            first = nw - nh
-        if n is None:
-            n = nw - first
-        steps = np.zeros(max(n, 0), np.int64)
-        values = np.zeros((max(n, 0), self._elem_history_sets, 24))
-        check(self.L.hakai_elem_history_read(self.ctx, int(first), int(n), ptr(steps, I64), ptr(values)))
-        return _elem_history_dict(steps, values)
+        return _elem_history_dict(*self._records(self.elem_history_count, self.L.hakai_elem_history_read,
+                                                 (self._elem_history_sets, 24), first, n))
 
     def elem_history_probe(self, sets=(), per_elem: bool = False) -> dict:
         """The record of the current state (hakai_elem_history_probe), with sets of its own: a dict by
         field name, (sets, 6) for S and E, (sets,) for the rest, ``values`` (sets, 24); with per_elem
         also ``per_elem`` (nElement, 20): V, V0, S[6], E[6], EQ, SE, PD, eqps_max, q_max, V / V0."""
-        n, off, elems = self._elem_sets(sets)
+        n, off, elems = self._record_sets(sets)
         values = np.zeros((n + 1, 24))
         pe = np.zeros((self.model.nElement, 20)) if per_elem else None
         check(self.L.hakai_elem_history_probe(self.ctx, n, ptr(off, I64), ptr(elems, I64), ptr(values), ptr(pe)))
@@ -590,48 +586,43 @@ def cal_triax_stress(integ_stress, integ_triax_stress, device: int = 0):
     check(lib().hakai_triax_stress(device, st.shape[0], ptr(st), ptr(integ_triax_stress)))
 
 
-def write_history_csv(path: str, set_names, steps, values, d_time: float):
-    """History records as CSV (hakai_history_write_csv): values (n, sets, 16), set 0's name first."""
+def _write_records_csv(write, F: int, path: str, set_names, steps, values, d_time: float):
     steps = np.ascontiguousarray(steps, np.int64)
     values = np.ascontiguousarray(values, np.float64)
     names = (ctypes.c_char_p * len(set_names))(*[str(s).encode() for s in set_names])
-    assert values.shape == (len(steps), len(set_names), 16), values.shape
-    check(lib().hakai_history_write_csv(str(path).encode(), len(set_names), names, len(steps), ptr(steps, I64),
-                                        ptr(values), float(d_time)))
+    assert values.shape == (len(steps), len(set_names), F), values.shape
+    check(write(str(path).encode(), len(set_names), names, len(steps), ptr(steps, I64), ptr(values), float(d_time)))
+
+
+def _read_records_csv(path: str, F: int, field0: str) -> dict:
+    with open(path) as fh:
+        head = fh.readline().strip().split(",")
+        rows = [ln.strip().split(",") for ln in fh if ln.strip()]
+    sets = [h[:-len("_" + field0)] for h in head[2::F]]
+    steps = np.array([int(r[0]) for r in rows], np.int64)
+    time = np.array([float(r[1]) for r in rows])
+    values = np.array([[float(x) for x in r[2:]] for r in rows]).reshape(len(rows), len(sets), F)
+    return dict(sets=sets, steps=steps, time=time, values=values)
+
+
+def write_history_csv(path: str, set_names, steps, values, d_time: float):
+    """History records as CSV (hakai_history_write_csv): values (n, sets, 16), set 0's name first."""
+    _write_records_csv(lib().hakai_history_write_csv, 16, path, set_names, steps, values, d_time)
 
 
 def read_history_csv(path: str) -> dict:
     """A history.csv back as dict(sets, steps, time, values (n, sets, 16)): the same doubles."""
-    with open(path) as fh:
-        head = fh.readline().strip().split(",")
-        rows = [ln.strip().split(",") for ln in fh if ln.strip()]
-    sets = [h[:-len("_F_int_x")] for h in head[2::16]]
-    steps = np.array([int(r[0]) for r in rows], np.int64)
-    time = np.array([float(r[1]) for r in rows])
-    values = np.array([[float(x) for x in r[2:]] for r in rows]).reshape(len(rows), len(sets), 16)
-    return dict(sets=sets, steps=steps, time=time, values=values)
+    return _read_records_csv(path, 16, "F_int_x")
 
 
 def write_elem_history_csv(path: str, set_names, steps, values, d_time: float):
     """Element-set records as CSV (hakai_elem_history_write_csv): values (n, sets, 24), set 0's name first."""
-    steps = np.ascontiguousarray(steps, np.int64)
-    values = np.ascontiguousarray(values, np.float64)
-    names = (ctypes.c_char_p * len(set_names))(*[str(s).encode() for s in set_names])
-    assert values.shape == (len(steps), len(set_names), 24), values.shape
-    check(lib().hakai_elem_history_write_csv(str(path).encode(), len(set_names), names, len(steps), ptr(steps, I64),
-                                             ptr(values), float(d_time)))
+    _write_records_csv(lib().hakai_elem_history_write_csv, 24, path, set_names, steps, values, d_time)
 
 
 def read_elem_history_csv(path: str) -> dict:
     """An elem_history.csv back as dict(sets, steps, time, values (n, sets, 24)): the same doubles."""
-    with open(path) as fh:
-        head = fh.readline().strip().split(",")
-        rows = [ln.strip().split(",") for ln in fh if ln.strip()]
-    sets = [h[:-len("_N_active")] for h in head[2::24]]
-    steps = np.array([int(r[0]) for r in rows], np.int64)
-    time = np.array([float(r[1]) for r in rows])
-    values = np.array([[float(x) for x in r[2:]] for r in rows]).reshape(len(rows), len(sets), 24)
-    return dict(sets=sets, steps=steps, time=time, values=values)
+    return _read_records_csv(path, 24, "N_active")
 
 
 MASS_SCALE_CSV = ("step", "dt_target", "n_active", "n_scaled", "n_changed", "n_capped", "n_unfixable", "mass_added",

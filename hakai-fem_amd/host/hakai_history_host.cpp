@@ -2,17 +2,18 @@
 // other part of the library: the CSV writer, the drivers' set definition (hakai_run_inp and the
 // N-GPU driver hakai.run take their sets from here, so they cannot drift), and the combination of
 // the ranks' partial records. Compiled without contraction: hakai_history_combine's sums are plain
-// additions in rank order. tools/history_host_check.cpp builds this file alone.
+// additions in rank order. The CSV loop and the refusals in front of the combination are
+// hakai_records_host.hpp's, shared with the element-set history. tools/history_host_check.cpp builds
+// this file alone.
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/hakai_hip.h"
+#include "hakai_records_host.hpp"
 
 namespace hkc {
-int fail(int code, const char* fmt, ...);
 void history_driver_sets(const hakai_inp_model_t* M, std::vector<std::string>& names, std::vector<int64_t>& off,
                          std::vector<int64_t>& nodes, std::vector<std::string>& dropped);
 }  // namespace hkc
@@ -59,24 +60,8 @@ int hakai_history_write_csv(const char* path, int32_t n_names, const char* const
     static const char* const field[HAKAI_HISTORY_FIELDS] = {"F_int_x", "F_int_y", "F_int_z", "F_ext_x", "F_ext_y", "F_ext_z",
                                                             "P_x",     "P_y",     "P_z",     "KE",      "W_int",   "W_ext",
                                                             "W_bc",    "U_x",     "U_y",     "U_z"};
-    if (!path || n_names < 1 || n_names > HAKAI_HISTORY_MAX_SETS + 1 || !set_names || n < 0 ||
-        (n > 0 && (!steps || !values)))
-        return fail(HAKAI_ERR_ARG, "history_write_csv: bad arguments");
-    FILE* fp = std::fopen(path, "w");
-    if (!fp) return fail(HAKAI_ERR_IO, "%s: cannot open for writing", path);
-    std::fprintf(fp, "step,time");
-    for (int s = 0; s < n_names; ++s)
-        for (int f = 0; f < HAKAI_HISTORY_FIELDS; ++f) std::fprintf(fp, ",%s_%s", set_names[s], field[f]);
-    std::fprintf(fp, "\n");
-    const size_t W = (size_t)n_names * HAKAI_HISTORY_FIELDS;
-    for (int64_t i = 0; i < n; ++i) {
-        std::fprintf(fp, "%lld,%.17g", (long long)steps[i], (double)steps[i] * d_time);
-        for (size_t j = 0; j < W; ++j) std::fprintf(fp, ",%.17g", values[(size_t)i * W + j]);
-        std::fprintf(fp, "\n");
-    }
-    const bool bad = std::ferror(fp) != 0;
-    if (std::fclose(fp) != 0 || bad) return fail(HAKAI_ERR_IO, "%s: write failed", path);
-    return 0;
+    return hkc::write_records_csv("history_write_csv", path, field, HAKAI_HISTORY_FIELDS, HAKAI_HISTORY_MAX_SETS, n_names,
+                                  set_names, n, steps, values, d_time);
 }
 
 int hakai_inp_history_sets(const hakai_inp_model_t* model, int32_t* n_sets, int64_t* set_off, int64_t* set_nodes,
@@ -104,16 +89,9 @@ int hakai_inp_history_sets(const hakai_inp_model_t* model, int32_t* n_sets, int6
 
 int hakai_history_combine(int32_t n_ranks, int32_t n_total, int64_t n, const int64_t* steps, const double* values,
                           const double* ke_seed, int64_t* steps_out, double* values_out, double* ke_seed_out) {
-    if (n_ranks < 1 || n_total < 1 || n_total > HAKAI_HISTORY_MAX_SETS + 1 || n < 0)
-        return fail(HAKAI_ERR_ARG, "history_combine: %d ranks, %d sets, %lld records", n_ranks, n_total, (long long)n);
-    if (!ke_seed || !ke_seed_out || (n > 0 && (!steps || !values || !steps_out || !values_out)))
-        return fail(HAKAI_ERR_ARG, "history_combine: null array");
-    for (int r = 1; r < n_ranks; ++r)
-        for (int64_t i = 0; i < n; ++i)
-            if (steps[(size_t)r * n + i] != steps[i])
-                return fail(HAKAI_ERR_STATE, "history_combine: record %lld is step %lld on rank 0 and step %lld on rank "
-                            "%d (stride and capacity must be the same on every rank)", (long long)i,
-                            (long long)steps[i], (long long)steps[(size_t)r * n + i], r);
+    if (int r = hkc::combine_check("history_combine", HAKAI_HISTORY_MAX_SETS, n_ranks, n_total, n, steps,
+                                   !steps || !values || !steps_out || !values_out, !ke_seed || !ke_seed_out))
+        return r;
     // ((p_0 + p_1) + p_2) + ... in rank order, one rounding per addition (no contraction in this file)
     const size_t W = (size_t)n * n_total * HAKAI_HISTORY_FIELDS;
     for (size_t j = 0; j < W; ++j) {
